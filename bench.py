@@ -12,6 +12,13 @@ python bench.py [--gpus N] [--steps K] [--warmup W]; N > 1 is launched by
 torch.distributed.run (one process per GPU; the data path is RCCL inside
 libgossip_hip.so, the control plane is dist.py's own TCP star, which only
 distributes the RCCL id and the timings: no PyTorch in this process).
+
+A plain run builds the overlay, warms up, times the K steps and prints the
+result line (its roofline object comes from the timed steps' own counters).
+--full adds what takes work of its own: the cpu_baseline legs (the OpenMP
+oracle on the workload itself, the per-peer harness) and the degree-distribution
+check of the overlay (config.degree_check).  --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
 import glob
@@ -67,7 +74,12 @@ def parse(argv=None):
                     help="bit order of the message table: as drawn, or grouped by spread speed "
                          "(overlay.spread_order)")
     ap.add_argument("--spread-hops", type=int, default=3, help="--message-order spread: key radius (1..3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the cpu_baseline legs and the "
+                         "degree-distribution check of the overlay")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64; dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline legs")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--cpu-log2n", type=int, default=None,
                     help="cpu_baseline: overlay size of the oracle's run (all messages, W = 64); default: the "
@@ -89,6 +101,8 @@ def parse(argv=None):
     ap.add_argument("--profile-steps", action="store_true",
                     help="print per-round stats of the last step to stderr")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps needs at least 1 timed step, --warmup at least 0")
     c5 = a.workload == "c5"
     if a.log2n is None:
         a.log2n = 26 if c5 else 24
@@ -304,25 +318,73 @@ def _fp(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:16]
 
 
-def job_record(eng, stats, m_total, job, partitioned):
-    """The whole run's record as the line reports it, so that 1-GPU and N-GPU
-    lines compare directly: per-round receivers / active counts and
-    fingerprints of the per-vertex digest and the per-message coverage /
-    forwards (a shard job: the combined job outputs; one GPU: the context's
-    own).  None for the vertex partition (each rank holds its slice)."""
+def job_outputs(eng, m_total, job, partitioned):
+    """(digest, coverage, forwards) of the last step as its caller reads them:
+    the per-vertex digest and the per-message coverage / forwards (a shard job:
+    the combined job outputs; one GPU: the context's own).  forwards is None
+    under churn without track_msg_forwards; the whole tuple is None for the
+    vertex partition (each rank holds its slice)."""
     if partitioned:
         return None
     dig = eng.job_digest() if job else eng.digest()
     cov = eng.job_coverage(m_total) if job else eng.coverage()
     try:
-        fwd = _fp(eng.job_forwards(m_total) if job else eng.forwards())
+        fwd = eng.job_forwards(m_total) if job else eng.forwards()
     except Exception as e:   # churn without track_msg_forwards: GP_ENOTRACK
         if getattr(e, "status", None) != -6:
             raise
         fwd = None
+    return dig, cov, fwd
+
+
+def job_record(stats, outputs):
+    """The whole run's record as the line reports it, so that 1-GPU and N-GPU
+    lines compare directly: per-round receivers / active counts and
+    fingerprints of job_outputs().  None for the vertex partition."""
+    if outputs is None:
+        return None
+    dig, cov, fwd = outputs
     return {"rounds": len(stats), "receivers": [int(s["receivers"]) for s in stats],
             "active": [int(s["active"]) for s in stats], "new_bits": [int(s["new_bits"]) for s in stats],
-            "digest_fp": _fp(dig), "coverage_fp": _fp(cov), "forwards_fp": fwd}
+            "digest_fp": _fp(dig), "coverage_fp": _fp(cov), "forwards_fp": None if fwd is None else _fp(fwd)}
+
+
+DUMP_STATS = ("injected", "new_bits", "receivers", "sends", "active", "crashed", "reports", "removals")
+DUMP_MAX_VERTICES = 1 << 20   # digest rows written: 3 float64 each, 24 MiB at most
+
+
+def dump_outputs(path, stats, outputs):
+    """--dump-outputs: what the last timed step returned to its caller, as
+    float64 .npy files under `path` (every value an integer below 2^53, so
+    exact), for comparing two builds output for output:
+      round_stats.npy      [rounds, len(DUMP_STATS)] the per-round protocol
+                           counters the step returns, columns as DUMP_STATS
+      coverage.npy         [messages] vertices that received each message
+      forwards.npy         [messages] forwards of each message (absent where
+                           the run does not track them: churn)
+      digest.npy           [k, 2] the per-vertex digest as its high and low 32
+                           bits, of the vertices listed in
+      digest_vertices.npy  [k] every vertex, or, above DUMP_MAX_VERTICES, a
+                           fixed seeded sample of them in ascending order.
+    The vertex partition keeps its per-vertex outputs on their ranks: only
+    round_stats.npy is written."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "round_stats.npy"),
+            np.array([[s[k] for k in DUMP_STATS] for s in stats], dtype=np.float64).reshape(-1, len(DUMP_STATS)))
+    if outputs is None:
+        return
+    dig, cov, fwd = outputs
+    np.save(os.path.join(path, "coverage.npy"), cov.astype(np.float64))
+    if fwd is not None:
+        np.save(os.path.join(path, "forwards.npy"), fwd.astype(np.float64))
+    if dig.size > DUMP_MAX_VERTICES:
+        verts = np.sort(np.random.default_rng(0).choice(dig.size, DUMP_MAX_VERTICES, replace=False))
+    else:
+        verts = np.arange(dig.size)
+    d = dig[verts]
+    np.save(os.path.join(path, "digest.npy"),
+            np.stack([d >> np.uint64(32), d & np.uint64(0xffffffff)], axis=1).astype(np.float64))
+    np.save(os.path.join(path, "digest_vertices.npy"), verts.astype(np.float64))
 
 
 def main():
@@ -349,8 +411,8 @@ def main():
     eng.build_chung_lu(n, args.dbar, args.gamma, args.seed)
     _, nnz, _, _ = eng.info()
     setup_s = build_s = time.perf_counter() - t0
-    # SURVEY.md §8a A9 on the overlay just built (outside the timed region)
-    deg = eng.check_degree(args.gamma)
+    # --full: SURVEY.md §8a A9 on the overlay just built (outside the timed region)
+    deg = eng.check_degree(args.gamma) if args.full else None
     t0 = time.perf_counter()
     s_world, s_rank = (emu[1], emu[0]) if emu else (world, rank)   # the message-shard job's ranks
     shards = s_world > 1 and (emu is not None or args.parallel == "messages")
@@ -434,7 +496,10 @@ def main():
                                                 "rows_written", "row_bytes", "atomics", "done_nb", "lm_rows", "aliased",
                                                 "crashed", "reports", "removals", "scan", "expand_ms", "kernel_ms", "exchange_ms")}),
                   file=sys.stderr)
-    record = job_record(eng, runs[-1], args.messages, job, world > 1 and not shards)
+    outputs = job_outputs(eng, args.messages, job, world > 1 and not shards)
+    record = job_record(runs[-1], outputs)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, runs[-1], outputs)
     comm = None
     if job:
         cn, _, xp = eng.shard_info()
@@ -475,8 +540,8 @@ def main():
                        "comm": comm,
                        "job": record,
                        "setup_s": round(setup_s, 2), "build_s": round(build_s, 2),
-                       "degree_check": {"gamma_hat": round(deg["gamma_hat"], 4), "kmin": deg["kmin"],
-                                        "gamma": args.gamma, "ok": bool(deg["ok"])}},
+                       "degree_check": deg and {"gamma_hat": round(deg["gamma_hat"], 4), "kmin": deg["kmin"],
+                                                "gamma": args.gamma, "ok": bool(deg["ok"])}},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                          "kernel": (f"k_expand<{eng.words}> (+ k_mklm in line-mask rounds)" if eng.words > 32 else
@@ -496,7 +561,7 @@ def main():
             out["roofline"]["traffic"] = traffic
             out["roofline"]["traffic_source"] = src
             out["roofline"]["traffic_over_alg"] = traffic / out["roofline"]["alg_bytes_per_launch"]
-        if world == 1 and not emu and not args.no_cpu_baseline:
+        if args.full and world == 1 and not emu and not args.no_cpu_baseline:
             # the GPU line first (stderr), so that a CPU leg killed for memory
             # does not take the measurement with it
             print("gpu line (before cpu_baseline): " + json.dumps(out), file=sys.stderr, flush=True)

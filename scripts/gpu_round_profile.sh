@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=gpurun_out/rp
 mkdir -p $O/pmc
-timeout -k 10 400 python -u bench.py --profile-steps > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 400 python -u bench.py --full --profile-steps > $O/bench.json 2> $O/bench.err || exit 1
 echo "bench ok"; cat $O/bench.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 bench.py --no-cpu-baseline --profile-steps > $O/trace.json 2> $O/trace.err || exit 1
 echo "trace ok"
