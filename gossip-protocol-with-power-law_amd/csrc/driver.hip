@@ -439,10 +439,8 @@ static int launch_expand(Ctx* c) {
   // as a degree-split round instead (its prefix probes are a fraction of the
   // arcs, its push half only the low-degree senders' arcs) -- but only when
   // the pull would be one: the conditions of unfiltered_now, arc_mask_now,
-  // prefilter_now and split_now below, for a pull (records: W = 64 only)
-#ifndef GP_SPLIT_NARROW
-#define GP_SPLIT_NARROW 1
-#endif
+  // prefilter_now and split_now below, for a pull (records: W = 64 only;
+  // 512-message shard 14.62 -> 14.16 ms, profiles/r04_ab_shards.txt)
   const bool pull_unfiltered = c->cfg.unfiltered_pct > 0 &&
                                senders * 100.0 >= (double)c->cfg.unfiltered_pct * (double)c->n;
   const bool pull_masked = !pull_unfiltered && c->cfg.arc_mask_permille > 0 &&
@@ -451,7 +449,7 @@ static int launch_expand(Ctx* c) {
                            c->words < 64 && !pull_unfiltered && !pull_masked && c->cfg.prefilter_pct > 0 &&
                            senders * 100.0 < (double)c->cfg.prefilter_pct * (double)c->n &&
                            senders * 1000.0 < (double)c->cfg.split_max_permille * (double)c->n;
-  const bool narrow_split = GP_SPLIT_NARROW && c->mode_push && pull_splits && est * c->cfg.push_ratio > (double)c->nnz;
+  const bool narrow_split = c->mode_push && pull_splits && est * c->cfg.push_ratio > (double)c->nnz;
   if (narrow_split) c->mode_push = false;
   c->push_est = est;
   if (c->mode_push && c->nloc() > 0)
@@ -482,19 +480,16 @@ static int launch_expand(Ctx* c) {
   // context: seenpop and done_at share the vertex index)
   // Narrow rows (W = 8 / 16: the message shards of 4- and 8-GPU jobs) take the
   // per-receiver kernel instead of the flat one in the thin late rounds (under
-  // 1/GP_NARROW_ND_DIV of the n x m bits still missing): its receivers go
+  // 1/NARROW_ND_DIV of the n x m bits still missing): its receivers go
   // eight / sixteen per wave step (dnb_groups, gather_groups), while the flat
   // kernel keeps the dense rounds, the last of which leaves a shard ~1 % short
-#ifndef GP_NARROW_ND
-#define GP_NARROW_ND 1
-#endif
-#ifndef GP_NARROW_ND_DIV
-#define GP_NARROW_ND_DIV 16
-#endif
+  // (profiles/r06_ab_narrow_nd.txt; a threshold of n*m/4 or n*m/2 was no
+  // better, n*m/2 slower: LEDGER.md "Receiver groups for the message shards")
+  constexpr double NARROW_ND_DIV = 16;
   const double nm = (double)c->n * (double)c->m;
-  c->narrow_pr_now = GP_NARROW_ND && (c->words == 8 || c->words == 16) && c->words <= c->cfg.flat_max_words &&
+  c->narrow_pr_now = (c->words == 8 || c->words == 16) && c->words <= c->cfg.flat_max_words &&
                      c->early_exit_now && !c->mode_push && !c->liveness_active && !c->local &&
-                     c->nloc() == c->n_alloc && (nm - (double)c->held_bits) * GP_NARROW_ND_DIV < nm;
+                     c->nloc() == c->n_alloc && (nm - (double)c->held_bits) * NARROW_ND_DIV < nm;
   c->dnb_now = c->early_exit_now && !c->mode_push && !c->liveness_active && !c->local &&
                c->nloc() == c->n_alloc && (c->words > c->cfg.flat_max_words || c->narrow_pr_now) &&
                (double)c->held_bits * 2.0 >= (double)c->n * (double)c->m;
@@ -516,11 +511,8 @@ static int launch_expand(Ctx* c) {
   // first aliasing round reads rows written before any alias and needs no
   // probe (C4 round 4: 74.6 M arcs whose probe would sit in each pass's
   // dependent chain).  A push round first writes its aliased senders' rows
-  // (k_unalias)
-#ifndef GP_ALIAS
-#define GP_ALIAS 1
-#endif
-  const bool alias_ok = GP_ALIAS && c->words == 64 && !c->liveness_active && !c->local && c->nloc() == c->n_alloc &&
+  // (k_unalias; profiles/r06_ab_alias.txt)
+  const bool alias_ok = c->words == 64 && !c->liveness_active && !c->local && c->nloc() == c->n_alloc &&
                         c->cfg.compact_rows == 0 && c->words > c->cfg.flat_max_words;
   c->alias_now = c->dnb_now && alias_ok;
   c->dprobe_now = c->alias_now && c->alias_active;
@@ -529,11 +521,8 @@ static int launch_expand(Ctx* c) {
   // neither done nor sated; a pull whose list is under a third of the
   // vertices launches waves for those alone, k_mkbits does every sender's
   // accounting and the receivers' fpop_next starts zeroed (C5 round 6: 1.26 M
-  // receivers of 64 M vertices)
-#ifndef GP_ULIST
-#define GP_ULIST 1
-#endif
-  const bool list_ok = GP_ULIST && !c->mode_push && !c->local && c->nloc() == c->n_alloc && c->words == 64 &&
+  // receivers of 64 M vertices; profiles/r06_ab_lists_c5.txt)
+  const bool list_ok = !c->mode_push && !c->local && c->nloc() == c->n_alloc && c->words == 64 &&
                        c->words > c->cfg.flat_max_words && c->cfg.compact_rows == 0 && c->early_exit_now;
 #ifndef GP_ULIST_DIV
 #define GP_ULIST_DIV 3
@@ -1104,17 +1093,6 @@ int gp_read(gp_ctx* c, int32_t what, void* host, int64_t bytes) {
                        hipMemcpyDeviceToHost));
       return 0;
     }
-#ifdef GP_DBG_READ   // scripts/debug_mask2.py: arc mask, gather-order columns, activity bits
-    case 100:
-      GP_TRY(copy_sync(c, host, c->d_amask, (size_t)bytes, hipMemcpyDeviceToHost));
-      return 0;
-    case 101:
-      GP_TRY(copy_sync(c, host, c->d_gcol, (size_t)bytes, hipMemcpyDeviceToHost));
-      return 0;
-    case 102:
-      GP_TRY(copy_sync(c, host, c->d_abits, (size_t)bytes, hipMemcpyDeviceToHost));
-      return 0;
-#endif
     case GP_FPOP:
       if (!run) return set_error(GP_ESTATE, "no run state");
       GP_TRY(need(n * 4));

@@ -1,5 +1,5 @@
 // gp_device.h -- device-side definitions shared by the kernel translation
-// units of libgossip_hip.so (pull.hip, hub.hip, push.hip, driver.hip): row
+// units of libgossip_hip.so (pull*.hip, hub.hip, push.hip, driver.hip): row
 // geometry, per-wave counters, the pull's argument block, the gather and
 // commit helpers every receiver side uses (k_expand, k_expand_flat, the hub
 // passes, k_apply), and the host launch entry points each unit defines.
@@ -936,6 +936,15 @@ inline bool state_ready(const Ctx* c) { return c->d_sp != nullptr && c->d_slot[0
 // pull.hip: every kernel of one expansion round (push or pull, hub passes,
 // the degree-split push half) for the context's row width
 int launch_round_kernels(Ctx* c, const ExpandArgs& a);
+// pull_flat.hip: the edge-parallel pull of narrow rows (W <= 32)
+template <int W> void launch_expand_flat_w(Ctx* c, const ExpandArgs& a);
+// pull_rec.hip: the pull that reads compact Message-List records (W = 64)
+void launch_expand_rec(Ctx* c, const ExpandArgs& a);
+// pull_aux.hip: the helper passes around a pull round
+void launch_mklm(Ctx* c, const ExpandArgs& a);        // line masks of the senders' rows
+void launch_arcmask(Ctx* c);                          // per-arc activity mask
+template <int W> void launch_fixup_rows_w(Ctx* c);    // unfiltered round: stale rows zeroed
+template <int W> void launch_park_w(Ctx* c);          // ... under liveness: crashed vertices' rows parked
 // push.hip
 template <int W> void launch_push_w(Ctx* c, ExpandArgs a);            // a push round
 template <int W> void launch_split_push_w(Ctx* c, const ExpandArgs& a);   // degree-split round: the push half

@@ -359,7 +359,7 @@ int alloc_exchange(Ctx* c);                    // exchange buffers for the curre
 int pack_boundary(Ctx* c);                     // after E_r: this round's boundary entries -> send buffers
 int exchange_rccl(Ctx* c);                     // counts, rows, alive sets over RCCL, then unpack
 int exchange_group(Ctx** ctxs, int32_t nctx);  // the same through device-to-device copies
-// pull.hip: write the component rows of aliased vertices (all, or this
+// pull_aux.hip: write the component rows of aliased vertices (all, or this
 // round's senders only) into S[cur]; with all, the run holds no alias after
 int unalias(Ctx* c, bool senders_only);
 // shard.hip

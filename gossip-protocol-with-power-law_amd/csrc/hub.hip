@@ -100,10 +100,8 @@ __global__ __launch_bounds__(HBLOCK) void k_hub_final(ExpandArgs a) {
       // component it lacked is sated, as k_expand marks its receivers.  Hubs
       // are the first in-neighbours of most gather orders, so their marks are
       // what the next round's done-neighbour probe finds
-#ifndef GP_HUB_SATE
-#define GP_HUB_SATE 1
-#endif
-      if (GP_HUB_SATE && a.sate && a.early_exit && a.alive) {
+      // (profiles/r06_ab_hub_sate.txt)
+      if (a.sate && a.early_exit && a.alive) {
         u64x2 rem = {0, 0};
         if (g == 0) {
           const u64x2 sv = load_seen<W>(a, v, a.sp[v], lw);

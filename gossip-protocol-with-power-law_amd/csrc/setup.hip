@@ -826,7 +826,6 @@ int gp_reset(gp_ctx* c) {
   c->last_reports = 0;
   c->alias_active = c->alias_now = c->dprobe_now = false;
   c->ulist_valid = c->ulist_emit_now = c->ulist_read_now = false;
-  c->ulist_valid = c->ulist_emit_now = c->ulist_read_now = false;
   shard_reset(c);
   GP_HIP(hipStreamSynchronize(s));
   return 0;

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Summarise a rocprofv3 --kernel-trace --stats run (rocpd .db or kernel_stats.csv)
-into a small markdown table for profiles/.  usage: prof_summary.py <db|csv> [title]"""
+into a small markdown table for profiles/.  usage: prof_summary.py <db|csv> [title]
+or, kernel name -> calls only: prof_summary.py --calls <db|csv> [<db|csv> ...]"""
 import csv
 import re
 import sqlite3
@@ -28,7 +29,22 @@ def rows_from(path):
     return out
 
 
+def calls_table(paths):
+    """kernel name -> calls over every process of a run: which kernels were
+    launched and how often, nothing about time (two builds that choose the
+    same variants everywhere give the same table)"""
+    calls = {}
+    for p in paths:
+        for name, n, _, _, _ in rows_from(p):
+            calls[short(name)] = calls.get(short(name), 0) + n
+    print("| kernel | calls |\n|---|---|")
+    for name in sorted(calls):
+        print(f"| `{name}` | {calls[name]} |")
+
+
 def main():
+    if sys.argv[1] == "--calls":
+        return calls_table(sys.argv[2:])
     path = sys.argv[1]
     title = sys.argv[2] if len(sys.argv) > 2 else path
     print(f"# {title}\n")
