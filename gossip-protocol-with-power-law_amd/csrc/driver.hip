@@ -871,9 +871,12 @@ int gp_round(gp_ctx* c, gp_round_stats* out) {
   if (!c) return set_error(GP_EINVAL, "null ctx");
   if (c->local && !c->comm)
     return set_error(GP_ESTATE, "a partitioned context exchanges over RCCL (gp_comm_init) or in gp_round_group");
+  // (message-shard job, shard.hip: the history check and its growth come
+  // first, so that no error of theirs can leave a round half applied)
+  if (c->jnranks > 0) GP_TRY(shard_prepare_round(c));
   GP_TRY(round_launch(c));
   GP_TRY(round_exchange_rccl(c));
-  if (c->jnranks > 0) GP_TRY(shard_record_round(c));   // (message-shard job: shard.hip)
+  if (c->jnranks > 0) GP_TRY(shard_record_round(c));
   return round_collect(c, out);
 }
 

@@ -280,8 +280,11 @@ struct Ctx {
   gp_allgather_fn jhost = nullptr;      // gp_shard_host_init
   void* jhost_user = nullptr;
   int32_t jrank = 0, jnranks = 0;
-  u64* d_hist = nullptr;                // [hist_cap][2][nwords]: round r's receivers, then senders
+  u64* d_hist = nullptr;                // [hist_cap][2][hist_nw]: round r's receivers, then senders
   int32_t hist_cap = 0, hist_rounds = 0;
+  int64_t hist_nw = 0;                  // bitmap words d_hist was allocated for (ceil(n_alloc / 64))
+  bool hist_valid = true;               // false: the run did not start at gp_reset in this job (restored from a
+                                        // checkpoint, transport joined in mid-run): no job record, rounds go on
   std::vector<gp_round_stats> run_stats;   // this run's rounds, as gp_round returned them
   int32_t fin_round = -1;               // round count at the last gp_finalize_messages of this run
   u64* d_jscr = nullptr;                // combine scratch (send / receive chunks)
@@ -363,6 +366,7 @@ int exchange_group(Ctx** ctxs, int32_t nctx);  // the same through device-to-dev
 // round's senders only) into S[cur]; with all, the run holds no alias after
 int unalias(Ctx* c, bool senders_only);
 // shard.hip
+int shard_prepare_round(Ctx* c);               // before round r of a shard job: history in step, room for r
 int shard_record_round(Ctx* c);                // after E_r of a shard job: round r's bitmaps
 void shard_free(Ctx* c);
 void shard_reset(Ctx* c);                      // new run (gp_reset, checkpoint load)

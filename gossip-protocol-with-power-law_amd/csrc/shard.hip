@@ -105,21 +105,52 @@ __global__ void k_shard_xor(const u64* __restrict__ in, int32_t P, int64_t L, in
 
 static int64_t hist_words(const Ctx* c) { return (c->n_alloc + 63) / 64; }
 
-int shard_record_round(Ctx* c) {
+// Before round r touches any state: a history that does not hold rounds
+// [0, r) -- the run was restored from a checkpoint, or the transport was set
+// in mid-run -- is dropped for the rest of the run (the rounds go on, the
+// rank's own outputs stay exact, gp_shard_combine refuses on every rank);
+// otherwise make room for round r, so that nothing can fail between
+// round_launch and round_collect.
+int shard_prepare_round(Ctx* c) {
+  if (!state_ready(c)) return 0;   // (round_launch reports it)
   const int r = c->round;
+  if (c->hist_valid && r != c->hist_rounds) c->hist_valid = false;
+  if (!c->hist_valid) return 0;
   const int64_t nw = hist_words(c);
-  if (r >= c->hist_cap) {   // grow (doubling): the rounds of a run are not known in advance
-    const int32_t cap = std::max(16, 2 * c->hist_cap);
-    u64* d = nullptr;
-    GP_TRY(dalloc(&d, (size_t)cap * 2 * nw));
-    if (c->d_hist && c->hist_rounds > 0)
-      GP_HIP(hipMemcpyAsync(d, c->d_hist, (size_t)c->hist_rounds * 2 * nw * 8, hipMemcpyDeviceToDevice, c->stream));
-    GP_HIP(hipStreamSynchronize(c->stream));
-    dfree(&c->d_hist);
-    c->d_hist = d;
-    c->hist_cap = cap;
+  const bool resized = nw != c->hist_nw;   // another overlay since the history was allocated
+  if (resized && r > 0) {                  // (gp_load_graph asks for a gp_reset: not reached)
+    c->hist_valid = false;
+    return 0;
   }
-  if (r != c->hist_rounds) return set_error(GP_ESTATE, "shard history out of step with the rounds");
+  if (r < c->hist_cap && !resized) return 0;
+  // grow (doubling): the rounds of a run are not known in advance
+  GP_HIP(hipSetDevice(c->device));
+  const int32_t cap = resized ? std::max(16, c->hist_cap) : std::max(16, 2 * c->hist_cap);
+  u64* d = nullptr;
+  GP_TRY(dalloc(&d, (size_t)cap * 2 * nw));
+  hipError_t e = hipSuccess;
+  if (c->d_hist && c->hist_rounds > 0 && !resized)
+    e = hipMemcpyAsync(d, c->d_hist, (size_t)c->hist_rounds * 2 * nw * 8, hipMemcpyDeviceToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    dfree(&d);
+    return set_error(GP_EHIP, std::string("shard history: ") + hipGetErrorString(e));
+  }
+  dfree(&c->d_hist);
+  c->d_hist = d;
+  c->hist_cap = cap;
+  c->hist_nw = nw;
+  return 0;
+}
+
+int shard_record_round(Ctx* c) {
+  if (!c->hist_valid) return 0;
+  const int r = c->round;
+  if (r != c->hist_rounds || r >= c->hist_cap || hist_words(c) != c->hist_nw) {   // (shard_prepare_round did not see this round)
+    c->hist_valid = false;
+    return 0;
+  }
+  const int64_t nw = hist_words(c);
   u64* rx = c->d_hist + (size_t)r * 2 * nw;
   hipLaunchKernelGGL(k_shard_hist, dim3(std::max(1, std::min(grid_for(nw, WAVES), c->cu_count * 8))), dim3(BLOCK),
                      0, c->stream, c->d_fpop[c->cur ^ 1], c->d_abits, rx, rx + nw, c->n_alloc);
@@ -130,6 +161,7 @@ int shard_record_round(Ctx* c) {
 
 void shard_reset(Ctx* c) {
   c->hist_rounds = 0;
+  c->hist_valid = true;   // (until a round finds the run ahead of it: shard_prepare_round)
   c->run_stats.clear();
   c->fin_round = -1;
   c->j_ready = false;
@@ -142,6 +174,7 @@ void shard_free(Ctx* c) {
   c->jnranks = 0;
   dfree(&c->d_hist);
   c->hist_cap = 0;
+  c->hist_nw = 0;
   dfree(&c->d_jscr);
   c->jscr_words = 0;
   dfree(&c->d_jdig);
@@ -217,9 +250,10 @@ constexpr int NF = 32;
 enum {
   F_INJECTED, F_LOST, F_NEW_BITS, F_RECEIVERS, F_SENDS, F_ACTIVE, F_CRASHED, F_REPORTS, F_REMOVALS, F_DUP,
   F_ARCS, F_GATHERED, F_SEEN_READ, F_WRITTEN, F_VISITED, F_ATOMICS, F_NEXT_ARCS, F_ROW_BYTES, F_XROWS, F_XBYTES,
-  F_DNB, F_LM_ROWS, F_OVERFLOW, F_MODE, F_SCAN, F_EXPAND_MS, F_EXCHANGE_MS, F_ROUND_MS, F_KERNEL_MS, F_RAN
+  F_DNB, F_LM_ROWS, F_OVERFLOW, F_MODE, F_SCAN, F_EXPAND_MS, F_EXCHANGE_MS, F_ROUND_MS, F_KERNEL_MS, F_RAN,
+  F_ALIASED
 };
-static_assert(F_RAN < NF, "counter words");
+static_assert(F_ALIASED < NF, "counter words");
 
 u64 dbits(double x) {
   u64 b;
@@ -242,18 +276,22 @@ void pack_stats(const gp_round_stats& s, u64* f) {
   f[F_ROW_BYTES] = s.row_bytes; f[F_XROWS] = s.xchg_rows; f[F_XBYTES] = s.xchg_bytes; f[F_DNB] = s.done_nb;
   f[F_LM_ROWS] = s.lm_rows; f[F_OVERFLOW] = (u64)s.overflow; f[F_MODE] = (u64)s.mode; f[F_SCAN] = (u64)s.scan;
   f[F_EXPAND_MS] = dbits(s.expand_ms); f[F_EXCHANGE_MS] = dbits(s.exchange_ms); f[F_ROUND_MS] = dbits(s.round_ms);
-  f[F_KERNEL_MS] = dbits(s.kernel_ms); f[F_RAN] = 1;
+  f[F_KERNEL_MS] = dbits(s.kernel_ms); f[F_RAN] = 1; f[F_ALIASED] = s.aliased;
 }
 
 // header words all-gathered first: every rank validates every rank's shape
 enum { H_N, H_NNZ, H_M, H_WORDS, H_WBASE, H_ROUNDS, H_DIGEST, H_FWD, H_CHURN, H_SEED, H_PFAIL, H_DIRECTED, H_OK,
-       NH = 16 };
+       H_CAP, NH = 16 };
+static_assert(H_CAP < NH, "header words");
 
+// (a failed growth keeps the scratch there was: the combine still needs its
+// first words to tell the other ranks)
 int ensure_scratch(Ctx* c, size_t words) {
   if (c->jscr_words >= words) return 0;
+  u64* d = nullptr;
+  GP_TRY(dalloc(&d, words));
   dfree(&c->d_jscr);
-  c->jscr_words = 0;
-  GP_TRY(dalloc(&c->d_jscr, words));
+  c->d_jscr = d;
   c->jscr_words = words;
   return 0;
 }
@@ -267,7 +305,7 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
   // every rank returns the same status instead of its peers waiting in a
   // collective it never enters
   std::string why;
-  if (own < 1 || (int32_t)c->run_stats.size() != own || c->hist_rounds != own)
+  if (own < 1 || (int32_t)c->run_stats.size() != own || !c->hist_valid || c->hist_rounds != own)
     why = "gp_shard_combine needs a run of gp_round / gp_run since gp_reset on this context (a run restored "
           "from a checkpoint has no per-round history)";
   else if (c->fin_round != c->round && gp_finalize_messages(static_cast<gp_ctx*>(c)) != 0)
@@ -284,13 +322,14 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
   hdr[H_CHURN] = (u64)c->cfg.churn; hdr[H_SEED] = c->cfg.churn_seed; hdr[H_PFAIL] = dbits(c->cfg.p_fail);
   hdr[H_DIRECTED] = (u64)c->directed;
   hdr[H_OK] = why.empty() ? 1 : 0;
+  hdr[H_CAP] = (u64)cap;
   GP_TRY(copy_sync(c, c->d_jscr, hdr.data(), NH * 8, hipMemcpyHostToDevice));
   GP_TRY(x.allgather(c->d_jscr, c->d_jscr + NH, NH));
   GP_TRY(copy_sync(c, all.data(), c->d_jscr + NH, all.size() * 8, hipMemcpyDeviceToHost));
   auto H = [&](int q, int k) { return all[(size_t)q * NH + k]; };
   // every rank checks the same words, so every rank returns the same status
   std::vector<int> order((size_t)P);
-  int32_t R = 0, wmax = 0;
+  int32_t R = 0, wmax = 0, capmin = cap;
   int64_t mt = 0;
   if (!why.empty()) return set_error(GP_ESTATE, why);
   for (int q = 0; q < P; ++q)
@@ -303,6 +342,7 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
     order[(size_t)q] = q;
     R = std::max(R, (int32_t)H(q, H_ROUNDS));
     wmax = std::max(wmax, (int32_t)H(q, H_WORDS));
+    capmin = std::min(capmin, (int32_t)H(q, H_CAP));
     mt += (int64_t)H(q, H_M);
   }
   std::sort(order.begin(), order.end(), [&](int a, int b) { return H(a, H_WBASE) < H(b, H_WBASE); });
@@ -316,7 +356,11 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
       next += (int64_t)H(q, H_M);
     }
   }
-  if (cap < R) return set_error(GP_EINVAL, "gp_shard_combine: cap < the job's rounds (" + std::to_string(R) + ")");
+  // the smallest cap of the job, so that a rank with room does not go on into
+  // collectives that a rank without has left
+  if (capmin < R)
+    return set_error(GP_EINVAL, "gp_shard_combine: cap " + std::to_string(capmin) + " < the job's rounds (" +
+                                    std::to_string(R) + ")");
   const int64_t n = c->n, nw = hist_words(c);
   const int32_t NB = 2 * R;   // bitmaps: per round receivers, senders
   const int64_t L = (nw + P - 1) / P;
@@ -329,7 +373,33 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
                o_cnta = o_cnt + NB, o_bs = o_cnta + (size_t)P * NB, o_br = o_bs + (size_t)P * NB * L,
                o_dr = o_br + (size_t)P * NB * L, o_ds = o_dr + (size_t)P * Ld, o_cf = o_ds + Ld,
                o_cfa = o_cf + 2 * MS, total = o_cfa + (size_t)P * 2 * MS;
-  GP_TRY(ensure_scratch(c, total));
+  // Every allocation of the combine happens here, and the ranks exchange how
+  // it went: a rank out of memory fails the job on every rank instead of
+  // leaving its peers in the collectives below.
+  const bool dig = H(0, H_DIGEST) != 0;
+  {
+    int rc = ensure_scratch(c, std::max(total, (size_t)NH * (P + 1)));
+    if (rc == 0 && dig && c->jdig_words != (size_t)P * Ld) {
+      c->jdig_words = 0;
+      rc = dalloc(&c->d_jdig, (size_t)P * Ld);
+      if (rc == 0) c->jdig_words = (size_t)P * Ld;
+    }
+    if (rc == 0 && (c->jm != (int32_t)mt || !c->d_jcf)) {
+      c->jm = 0;
+      rc = dalloc(&c->d_jcf, 2 * (size_t)std::max<int64_t>(mt, 1));
+      if (rc == 0) c->jm = (int32_t)mt;
+    }
+    const std::string err = rc ? gp_last_error() : "";
+    const u64 ok = rc == 0 ? 1 : 0;
+    std::vector<u64> oks((size_t)P);
+    GP_TRY(copy_sync(c, c->d_jscr, &ok, 8, hipMemcpyHostToDevice));
+    GP_TRY(x.allgather(c->d_jscr, c->d_jscr + 1, 1));
+    GP_TRY(copy_sync(c, oks.data(), c->d_jscr + 1, (size_t)P * 8, hipMemcpyDeviceToHost));
+    if (rc) return set_error(GP_ENOMEM, "gp_shard_combine: " + err);
+    for (int q = 0; q < P; ++q)
+      if (!oks[(size_t)q])
+        return set_error(GP_ENOMEM, "gp_shard_combine: rank " + std::to_string(q) + " is out of device memory");
+  }
   u64* S = c->d_jscr;
 
   // 2. per-round counters of every rank
@@ -356,14 +426,7 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
   GP_TRY(x.allgather(S + o_cnt, S + o_cnta, (size_t)NB));
 
   // 4. digests: XOR reduce-scatter over vertex slices, then all-gather the slices
-  const bool dig = H(0, H_DIGEST) != 0;
   if (dig) {
-    if (c->jdig_words != (size_t)P * Ld) {
-      dfree(&c->d_jdig);
-      c->jdig_words = 0;
-      GP_TRY(dalloc(&c->d_jdig, (size_t)P * Ld));
-      c->jdig_words = (size_t)P * Ld;
-    }
     std::vector<size_t> soff((size_t)P), sw((size_t)P), roff((size_t)P), rw((size_t)P, (size_t)lend);
     for (int q = 0; q < P; ++q) {
       soff[(size_t)q] = (size_t)q * Ld;
@@ -384,10 +447,6 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
     GP_HIP(hipMemcpyAsync(S + o_cf, c->d_msg_cov + 2 * MM, (size_t)c->m * 8, hipMemcpyDeviceToDevice, s));
     GP_HIP(hipMemcpyAsync(S + o_cf + MS, c->d_msg_cov + 3 * MM, (size_t)c->m * 8, hipMemcpyDeviceToDevice, s));
     GP_TRY(x.allgather(S + o_cf, S + o_cfa, 2 * MS));
-    if (c->jm != (int32_t)mt || !c->d_jcf) {
-      dfree(&c->d_jcf);
-      GP_TRY(dalloc(&c->d_jcf, 2 * (size_t)std::max<int64_t>(mt, 1)));
-    }
     for (int q = 0; q < P; ++q) {
       const size_t at = (size_t)H(q, H_WBASE) * 64, mq = (size_t)H(q, H_M);
       for (int k = 0; k < 2; ++k)
@@ -425,7 +484,7 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
       o.arcs_scanned += f[F_ARCS]; o.rows_gathered += f[F_GATHERED]; o.seen_rows_read += f[F_SEEN_READ];
       o.rows_written += f[F_WRITTEN]; o.vertices_visited += f[F_VISITED]; o.atomics += f[F_ATOMICS];
       o.next_arcs += f[F_NEXT_ARCS]; o.row_bytes += f[F_ROW_BYTES]; o.xchg_rows += f[F_XROWS];
-      o.xchg_bytes += f[F_XBYTES]; o.done_nb += f[F_DNB]; o.lm_rows += f[F_LM_ROWS];
+      o.xchg_bytes += f[F_XBYTES]; o.done_nb += f[F_DNB]; o.lm_rows += f[F_LM_ROWS]; o.aliased += f[F_ALIASED];
       o.overflow |= (int32_t)f[F_OVERFLOW];
       o.expand_ms = std::max(o.expand_ms, dval(f[F_EXPAND_MS]));
       o.exchange_ms = std::max(o.exchange_ms, dval(f[F_EXCHANGE_MS]));

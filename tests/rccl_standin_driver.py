@@ -20,6 +20,15 @@ missing stream dependency in the engine shows up as a mismatch.
 --corrupt: one P = 2 case with GP_STANDIN_CORRUPT set by the caller (the
 stand-in overwrites one received boundary entry); every rank must fail the
 same round with GP_ERCCL and no rank may hang.  Prints "corrupt ok: ...".
+
+--shards: message-shard jobs through gp_shard_combine ("shard cases ok: N").
+
+--shard-edges: the edges of the job record over the RCCL code path (the same
+cases as tests/test_gpu_shard_job.py runs over the host transport): a run
+long enough for the history to grow, ranks whose runs end far apart, an
+overlay smaller than the job (zero-word ncclSend / ncclRecv pairs are skipped
+on both sides) and a rank restored from a checkpoint inside a job.  Prints
+"shard edge cases ok: N".
 """
 import os
 import sys
@@ -317,6 +326,113 @@ def shards(pkg):
     print(f"shard cases ok: {cases}", flush=True)
 
 
+def restore_then_refuse(pkg, g, origin, inject, cfg, okw):
+    """P = 2 over the stand-in RCCL: every rank runs 2 rounds, saves a
+    checkpoint, loads it back and runs on.  Its own outputs equal the oracle's
+    run of its block, the ranks' digests XOR into the whole table's, and the
+    combine fails with GP_ESTATE on every rank (none waits for the other)."""
+    m, P = len(origin), 2
+    whole = oracle.run(g, origin, inject, **okw)
+    uid = pkg.GossipEngine.comm_unique_id()
+    engs, refs = [], []
+    for k in range(P):
+        e = pkg.GossipEngine(0, **cfg)
+        e.load_graph(g)
+        lo, hi = pkg.dist.message_shard(m, P, k)
+        e.set_message_shard(origin, inject, lo, hi)
+        e.reset()
+        engs.append(e)
+        refs.append(oracle.run(g, origin[lo:hi], inject[lo:hi], want_first=True, **okw))
+    out = [None] * P
+
+    def rank(k):
+        try:
+            e, ref = engs[k], refs[k]
+            lo, hi = pkg.dist.message_shard(m, P, k)
+            last = int(inject[lo:hi].max())
+            e.shard_comm_init(uid, P, k)
+            stats = [e.round(), e.round()]
+            e.restore(e.checkpoint())
+            while not (stats[-1]["new_bits"] == 0 and stats[-1]["round"] >= last):
+                stats.append(e.round())
+            e.finalize()
+            assert len(stats) == ref["rounds"], (k, len(stats), ref["rounds"])
+            for a, b in zip(stats[2:], ref["stats"][2:]):
+                for key in STAT_KEYS:
+                    assert a[key] == b[key], (k, key, a["round"], a[key], b[key])
+            assert np.array_equal(e.seen(), ref["seen"][:, :e.words]), k
+            assert np.array_equal(e.first(), ref["first"]), k
+            assert np.array_equal(e.coverage(), ref["coverage"]), k
+            assert np.array_equal(e.forwards(), ref["forwards"]), k
+            if lo == 0:
+                assert np.array_equal(e.digest(), ref["digest"]), k
+            status = 0
+            try:
+                e.combine()
+            except pkg.GossipError as x:
+                status = x.status
+            out[k] = (status, e.digest())
+        except BaseException as exc:
+            out[k] = exc
+
+    ts = [threading.Thread(target=rank, args=(k,)) for k in range(P)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join(timeout=120)
+    assert not any(t.is_alive() for t in ts), "a rank hung in the combine"
+    for e in engs:
+        e.close()
+    assert not any(isinstance(o, BaseException) for o in out), [repr(o) for o in out]
+    assert [o[0] for o in out] == [pkg._lib.GP_ESTATE] * P, [o[0] for o in out]
+    assert np.array_equal(out[0][1] ^ out[1][1], whole["digest"])
+
+
+def shard_edges(pkg):
+    """The edge cases of tests/test_gpu_shard_job.py that depend on the
+    transport, over the stand-in RCCL."""
+    cases = 0
+    ring = [(i, (i + 1) % 131) for i in range(131)]
+    inject = (np.arange(130) % 3).astype(np.int32)
+    # a ring: 68 rounds on every rank, the history grows 16 -> 128
+    g = pkg.CSR.from_edges(131, ring)
+    origin = pkg.overlay.random_origins(131, 130, seed=7)
+    ref = oracle.run(g, origin, inject)
+    assert ref["rounds"] > 64, ref["rounds"]
+    check_shards(pkg, g, origin, inject, 3, [], {}, ref, "rccl", "edges ring131 P=3")
+    cases += 1
+    print("ok  history growth P=3", flush=True)
+    # ring + path, churn: the ranks' runs end 57 rounds apart
+    g = pkg.CSR.from_edges(134, ring + [(131, 132), (132, 133)])
+    rng = np.random.Generator(np.random.PCG64(11))
+    origin = np.concatenate([rng.integers(131, 134, 64), rng.integers(0, 131, 66)]).astype(np.int32)
+    ref = oracle.run(g, origin, inject, churn=True, p_fail=0.004, churn_seed=5)
+    own = [oracle.run(g, origin[lo:hi], inject[lo:hi], churn=True, p_fail=0.004, churn_seed=5)["rounds"]
+           for lo, hi in ((0, 64), (64, 130))]
+    assert abs(own[0] - own[1]) > 16, own
+    cfg = dict(churn=1, p_fail=0.004, churn_seed=5, track_msg_forwards=1)
+    check_shards(pkg, g, origin, inject, 2, [], cfg, ref, "rccl", "edges ring+path churn P=2")
+    cases += 1
+    print(f"ok  unequal runs P=2 (own rounds {own})", flush=True)
+    # 5 vertices, 8 ranks: one bitmap word, digest slices of one vertex, ranks 5-7 empty
+    g = pkg.CSR.from_edges(5, [(0, 1), (1, 2), (2, 3)])
+    origin = pkg.overlay.random_origins(5, 502, seed=3)
+    ref = oracle.run(g, origin, None)
+    check_shards(pkg, g, origin, None, 8, [], {}, ref, "rccl", "edges n=5 P=8")
+    cases += 1
+    print("ok  overlay smaller than the job P=8", flush=True)
+    # restored ranks run on; the combine refuses on every rank
+    g = pkg.overlay.barabasi_albert(3001, 2, seed=8)
+    origin = pkg.overlay.random_origins(g.n, 200, seed=8)
+    inject = (np.arange(200) % 4).astype(np.int32)
+    restore_then_refuse(pkg, g, origin, inject, dict(track_first=1, track_msg_forwards=1, churn=1, p_fail=0.02,
+                                                     churn_seed=3),
+                        dict(churn=True, p_fail=0.02, churn_seed=3))
+    cases += 1
+    print("ok  restore then refuse P=2", flush=True)
+    print(f"shard edge cases ok: {cases}", flush=True)
+
+
 def main():
     pkg = _gossip_pkg.load()
     lib_path = pkg._lib.load()._name
@@ -328,6 +444,9 @@ def main():
         return
     if "--shards" in sys.argv:
         shards(pkg)
+        return
+    if "--shard-edges" in sys.argv:
+        shard_edges(pkg)
         return
     cases = 0
     # small BA overlay: every P, slice rule, churn setting and mode

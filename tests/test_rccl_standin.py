@@ -98,3 +98,18 @@ def test_shard_job_combine_multi_rank(pkg, mode):
     with and without churn (Peer.py:175-216, each peer's whole receive record)."""
     out = _driver(pkg, mode, "--shards", timeout=580)
     assert "shard cases ok: 24" in out
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("mode", ["sync", "async"])
+def test_shard_job_edges_multi_rank(pkg, mode):
+    """The edges of the job record over the RCCL code path (csrc/shard.hip's
+    grouped ncclSend / ncclRecv and all-gathers; tests/test_gpu_shard_job.py
+    runs them over the host transport): 68 rounds at P = 3 (the history grows
+    three times), ranks whose runs end 57 rounds apart under churn, 5 vertices
+    for 8 ranks (empty slices: zero-word sends and receives are skipped on
+    both sides), and P = 2 ranks restored from a checkpoint, whose own outputs
+    stay exact while the combine fails with GP_ESTATE on both."""
+    out = _driver(pkg, mode, "--shard-edges", timeout=280)
+    assert "shard edge cases ok: 4" in out
