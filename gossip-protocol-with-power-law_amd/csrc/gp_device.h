@@ -29,7 +29,9 @@ constexpr int GS = 256 / BLOCK;     // grid-stride kernels' blocks per CU scale:
 #endif
 constexpr int EBLOCK = GP_EXPAND_BLOCK;
 constexpr int EWAVES = EBLOCK / 64;
-// the hub passes keep 4-wave blocks (64 threads measured equal, r04_ab_hub_block.txt)
+// the hub passes keep 4-wave blocks (64 threads measured equal on their own,
+// r04_ab_hub_block.txt; the chunks, which run beside the pull kernel, take
+// one-wave blocks: hub.hip)
 constexpr int HBLOCK = 256;
 constexpr int HWAVES = HBLOCK / 64;
 constexpr int NPART = 2048;        // partial stat slots (spread the atomics)
@@ -216,6 +218,8 @@ struct ExpandArgs {
   int32_t wbase;                       // global word index of local word 0 (message shards)
   int32_t rr;                          // receipt round of this expansion (r + 1)
   int32_t hub_thr;
+  const int32_t* __restrict__ border;  // k_expand (not SCAN_LIST): the block of 64 vertices the k-th wave
+                                       //   takes, long in-lists first (block_order.h; null: block k)
 };
 
 constexpr uint8_t SLOT_NONE = 0xFF;
@@ -949,8 +953,11 @@ template <int W> void launch_park_w(Ctx* c);          // ... under liveness: cra
 template <int W> void launch_push_w(Ctx* c, ExpandArgs a);            // a push round
 template <int W> void launch_split_push_w(Ctx* c, const ExpandArgs& a);   // degree-split round: the push half
 template <int W> void launch_acc_clear_w(Ctx* c);                     // ... and its accumulator back to zero
-// hub.hip: the hub receivers of a pull round (partials, then the final rows)
-template <int W> void launch_hubs_w(Ctx* c, const ExpandArgs& a, bool unfiltered, bool lines);
+// hub.hip: the hub receivers of a pull round -- the chunks' partial rows (on
+// stream s: beside the round's main pull kernel), then the final rows (on the
+// engine stream, after both)
+template <int W> void launch_hub_partial_w(Ctx* c, const ExpandArgs& a, bool unfiltered, bool lines, hipStream_t s);
+template <int W> void launch_hub_final_w(Ctx* c, const ExpandArgs& a);
 // liveness.hip: L_r (crash draws, miss counters, detection, seed removal)
 int launch_liveness(Ctx* c);
 constexpr int DET_CAP = 16384;   // deferred (big) detection candidates per round (more: walked in-wave)

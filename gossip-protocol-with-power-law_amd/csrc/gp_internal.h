@@ -48,6 +48,12 @@ struct Ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev[6] = {};
+  // side stream of the pull rounds (pull.hip launch_expand_w): the hub chunks
+  // run on it beside the round's main pull kernel, between ev_fork (recorded
+  // on the engine stream) and ev_join (which the engine stream waits for).
+  // Nothing else is ever enqueued on it
+  hipStream_t side = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   gp_config cfg{};
 
   // graph (full, replicated on every rank)
@@ -270,6 +276,9 @@ struct Ctx {
   u64* d_hub_partial = nullptr;  // [items][W]
   uint32_t* d_hub_pnz = nullptr;      // [items]
   int64_t n_hubs = 0, n_hub_items = 0;
+  // [ceil(nloc / 64)] launch order of k_expand's blocks: the blocks with a long
+  // non-hub in-list first (block_order.h; rebuilt with the hub table)
+  int32_t* d_border = nullptr;
 
   // rccl
   ncclComm_t comm = nullptr;

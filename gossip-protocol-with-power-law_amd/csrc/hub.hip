@@ -1,7 +1,10 @@
 // hub.hip -- hub receivers of the pull (hub load balancing):
 // vertices above hub_threshold in-arcs are split over waves, each wave ORs one
 // chunk of the in-list into a partial row (k_hub_partial), k_hub_final combines
-// a hub's partials and commits the row.  No atomics on rows, and the rows are
+// a hub's partials and commits the row.  The chunks read only state from before
+// the round and write only the partials, so they run on the context's side
+// stream beside the round's main pull kernel (pull.hip launch_expand_w);
+// k_hub_final follows both.  No atomics on rows, and the rows are
 // deterministic: every chunk's OR is a subset of the hub's new bits, so the OR
 // of the partials is exact whichever chunks stopped early.  The work counters
 // are not: in early-exit rounds a chunk that covers the hub's target stamps
@@ -12,17 +15,27 @@
 
 namespace gp {
 
+// The chunks run in one-wave blocks: beside the main pull kernel, whose
+// one-wave blocks take every slot as it frees, a 4-wave block waits for four
+// free slots on one CU and the chunks trickle in until the main kernel ends
+// (C4 round 3's chunks ended at 15.5 ms of a 15.4-ms main kernel against 1.3 ms
+// of 16.0, and C5's round 3, its main kernel slowed by the waiting blocks, ran
+// 76.6 against 73.2 ms: profiles/r08_ab_pull_schedule.txt, r08_c4_kernel_stats.md).
+// k_hub_final keeps HBLOCK
+constexpr int HPBLOCK = 64;
+constexpr int HPWAVES = HPBLOCK / 64;
+
 // hubs, pass 1: one wave per (hub, arc chunk) -> partial OR row
 template <int W, int MODE>
-__global__ __launch_bounds__(HBLOCK) void k_hub_partial(ExpandArgs a) {
+__global__ __launch_bounds__(HPBLOCK) void k_hub_partial(ExpandArgs a) {
   constexpr int LPR = Geo<W>::LPR;
-  __shared__ WaveLds s_w[HWAVES];
+  __shared__ WaveLds s_w[HPWAVES];
   const int lane = threadIdx.x & 63;
   const int wib = uniform(threadIdx.x >> 6);
   const int g = lane / LPR, lw = lane % LPR;
   WaveStats st;
-  ws_zero(st);
-  const int64_t it = (int64_t)blockIdx.x * HWAVES + wib;
+  ws_zero<HPWAVES>(st);
+  const int64_t it = (int64_t)blockIdx.x * HPWAVES + wib;
   if (it < a.n_items) {
     const HubItem h = a.hub_items[it];
     const int64_t i = h.v - a.vbegin;
@@ -65,7 +78,7 @@ __global__ __launch_bounds__(HBLOCK) void k_hub_partial(ExpandArgs a) {
     if (nz && g == 0) store_piece<W>(a.hub_partial, it, lw, acc);
     if (lane == 0) a.hub_pnz[it] = nz ? 1u : 0u;
   }
-  flush_stats(st, a.partial);
+  flush_stats<HPWAVES>(st, a.partial);
 }
 
 // hubs, pass 2: one wave per hub -> OR the partials, then the receiver side
@@ -121,31 +134,33 @@ __global__ __launch_bounds__(HBLOCK) void k_hub_final(ExpandArgs a) {
 // chunks probe the same masks and gather only the named 128-B lines: round 2
 // C4 12.85 -> 12.70 ms, C5 42.35 -> 40.99 ms, profiles/r05_ab_hub_lines.txt)
 template <int W>
-void launch_hubs_w(Ctx* c, const ExpandArgs& a, bool unfiltered, bool lines) {
+void launch_hub_partial_w(Ctx* c, const ExpandArgs& a, bool unfiltered, bool lines, hipStream_t s) {
   ExpandArgs h = a;
   h.n_items = c->n_hub_items;
-  const dim3 grid(grid_for(h.n_items, HWAVES));
+  const dim3 grid(grid_for(h.n_items, HPWAVES));
   bool done = false;
   if constexpr (W == 64) {
     if (lines && !unfiltered) {
-      hipLaunchKernelGGL((k_hub_partial<W, SCAN_FILTERED | SCAN_LINES>), grid, dim3(HBLOCK), 0, c->stream, h);
+      hipLaunchKernelGGL((k_hub_partial<W, SCAN_FILTERED | SCAN_LINES>), grid, dim3(HPBLOCK), 0, s, h);
       done = true;
     }
   }
   if (done) {
   } else if (unfiltered)
-    hipLaunchKernelGGL((k_hub_partial<W, SCAN_UNFILTERED>), grid, dim3(HBLOCK), 0, c->stream, h);
+    hipLaunchKernelGGL((k_hub_partial<W, SCAN_UNFILTERED>), grid, dim3(HPBLOCK), 0, s, h);
   else
-    hipLaunchKernelGGL((k_hub_partial<W, SCAN_FILTERED>), grid, dim3(HBLOCK), 0, c->stream, h);
+    hipLaunchKernelGGL((k_hub_partial<W, SCAN_FILTERED>), grid, dim3(HPBLOCK), 0, s, h);
+}
+template <int W>
+void launch_hub_final_w(Ctx* c, const ExpandArgs& a) {
+  ExpandArgs h = a;
   h.n_items = c->n_hubs;
   hipLaunchKernelGGL(k_hub_final<W>, dim3(grid_for(h.n_items, HWAVES)), dim3(HBLOCK), 0, c->stream, h);
 }
-template void launch_hubs_w<1>(Ctx*, const ExpandArgs&, bool, bool);
-template void launch_hubs_w<2>(Ctx*, const ExpandArgs&, bool, bool);
-template void launch_hubs_w<4>(Ctx*, const ExpandArgs&, bool, bool);
-template void launch_hubs_w<8>(Ctx*, const ExpandArgs&, bool, bool);
-template void launch_hubs_w<16>(Ctx*, const ExpandArgs&, bool, bool);
-template void launch_hubs_w<32>(Ctx*, const ExpandArgs&, bool, bool);
-template void launch_hubs_w<64>(Ctx*, const ExpandArgs&, bool, bool);
+#define V(W)                                                                                   \
+  template void launch_hub_partial_w<W>(Ctx*, const ExpandArgs&, bool, bool, hipStream_t);     \
+  template void launch_hub_final_w<W>(Ctx*, const ExpandArgs&);
+V(1) V(2) V(4) V(8) V(16) V(32) V(64)
+#undef V
 
 }  // namespace gp

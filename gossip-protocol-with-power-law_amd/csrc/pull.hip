@@ -48,7 +48,17 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
   constexpr bool GGROUPS = (W == 32 || W == 16) && QUADS && !ALIVE && SCAN == SCAN_UNFILTERED && !LIST;
   WaveStats st;
   ws_zero<EWAVES>(st);
-  const int64_t base = ((int64_t)blockIdx.x * EWAVES + wib) * 64;
+  // the wave's block of 64 vertices: the blocks with a long non-hub in-list are
+  // launched first (a.border, block_order.h: one wave-uniform load), so their
+  // chains do not start when the rest of the grid has drained; list rounds keep
+  // the list's order.  Nothing depends on the order: every receiver is
+  // committed by exactly one wave, the counters are sums, the next list is
+  // appended in atomic order
+  int64_t blk = (int64_t)blockIdx.x * EWAVES + wib;
+  if constexpr (!LIST) {
+    if (a.border && blk * 64 < a.nloc) blk = uniform(a.border[blk]);
+  }
+  const int64_t base = blk * 64;
   if (base < (LIST ? a.ulist_n : a.nloc)) {
     const int64_t li = base + lane;
     // lane's vertex (local index): base + lane, or the list's entry (list
@@ -497,11 +507,30 @@ static PullChoice choose_pull(const Ctx* c, const ExpandArgs& a, int W) {
   return p;
 }
 
+// One pull round on the engine stream, with the hub chunks on the context's
+// side stream beside the main pull kernel.  What orders what:
+//  - k_hub_partial reads only state from before the round (S[cur], sp,
+//    seenpop, state and done_at of hubs, the activity / line / done masks) and
+//    what the passes before the fork prepare: k_park, k_fixup_rows, k_arcmask,
+//    the degree-split push half, k_mklm.  It writes only hub_partial, hub_pnz,
+//    hub_done and atomically added stat partials.  The main pull kernel writes
+//    none of what it reads: commit_vertices writes `need` lanes only, and a hub
+//    is never `need`.  So the chunks wait for the fork alone, and are launched
+//    first: their chains are as long as the main kernel's longest.
+//  - k_hub_final reads the partials and ORs the hub's nibble into the lm_next
+//    byte the main kernel's commit wrote: it follows the join and the main
+//    kernel, on the engine stream.
+//  - everything after the round (stats reduce, exchange, readers, checkpoint,
+//    the next round) is enqueued on the engine stream behind the join; the next
+//    round's fork is recorded there after this round's k_hub_final, so the
+//    partial buffers are not overwritten while it reads them.
+// kernel_ms (ev[4] .. ev[5]) stays on the engine stream around all of it.
+enum { PULL_OK = 0, PULL_NOT_BUILT = 1, PULL_ORDER_FAILED = 2 };
 template <int W>
-static bool launch_expand_w(Ctx* c, ExpandArgs a) {   // false: the chosen pull kernel is not built for W
+static int launch_expand_w(Ctx* c, ExpandArgs a) {
   if (c->mode_push) {
     launch_push_w<W>(c, a);
-    return true;
+    return PULL_OK;
   }
   if (a.unfiltered && c->liveness_active) launch_park_w<W>(c);
   if (a.unfiltered) launch_fixup_rows_w<W>(c);
@@ -514,43 +543,57 @@ static bool launch_expand_w(Ctx* c, ExpandArgs a) {   // false: the chosen pull 
   if (a.prehi) launch_split_push_w<W>(c, a);   // degree-split round, push half: senders of in-degree < split_deg
   // line masks of the senders' rows (inside the pull's events and bytes)
   if (p.lines && !p.lm_from_commits) launch_mklm(c, a);   // (the last round's commits did not write them)
-  bool ok = true;
-  switch (p.kernel) {
-    case PULL_FLAT:
-      if constexpr (W <= 32) launch_expand_flat_w<W>(c, a);
-      else ok = false;
-      break;
-    case PULL_LIST: ok = launch_k_expand<W>(c, a, a.ulist_n, p.mode); break;
-    case PULL_RECEIVER: ok = launch_k_expand<W>(c, a, a.nloc, p.mode); break;
-    case PULL_RECORD: launch_expand_rec(c, a); break;
-    case PULL_NONE: break;
-  }
   if (p.mode & SCAN_LINES) {
     c->lines_ran = true;
     c->lines_from_commits = p.lm_from_commits;
   }
-  if (c->n_hub_items > 0) launch_hubs_w<W>(c, a, a.unfiltered != 0, c->lines_ran);
-  // kernel_ms brackets the pull kernel and the hub passes: the round's
-  // counters (row bytes, arcs scanned, rows written) include the hubs' share
+  const bool hubs = c->n_hub_items > 0;
+  bool order_ok = true;
+  if (hubs) {   // fork: the chunks first, their chains are the round's longest
+    order_ok = hipEventRecord(c->ev_fork, c->stream) == hipSuccess &&
+               hipStreamWaitEvent(c->side, c->ev_fork, 0) == hipSuccess;
+    if (order_ok) {
+      launch_hub_partial_w<W>(c, a, a.unfiltered != 0, c->lines_ran, c->side);
+      order_ok = hipEventRecord(c->ev_join, c->side) == hipSuccess;
+    }
+  }
+  int rc = PULL_OK;
+  switch (p.kernel) {
+    case PULL_FLAT:
+      if constexpr (W <= 32) launch_expand_flat_w<W>(c, a);
+      else rc = PULL_NOT_BUILT;
+      break;
+    case PULL_LIST: if (!launch_k_expand<W>(c, a, a.ulist_n, p.mode)) rc = PULL_NOT_BUILT; break;
+    case PULL_RECEIVER: if (!launch_k_expand<W>(c, a, a.nloc, p.mode)) rc = PULL_NOT_BUILT; break;
+    case PULL_RECORD: launch_expand_rec(c, a); break;
+    case PULL_NONE: break;
+  }
+  if (hubs) {   // join, then the hubs' rows
+    order_ok = order_ok && hipStreamWaitEvent(c->stream, c->ev_join, 0) == hipSuccess;
+    // kernel_ms brackets the pull kernel and the hub passes: the round's
+    // counters (row bytes, arcs scanned, rows written) include the hubs' share
+    if (order_ok) launch_hub_final_w<W>(c, a);
+  }
   if (a.prehi) launch_acc_clear_w<W>(c);   // degree-split round: the accumulator back to all-zero
   (void)hipEventRecord(c->ev[5], c->stream);
-  return ok;
+  return order_ok ? rc : PULL_ORDER_FAILED;
 }
 
 int launch_round_kernels(Ctx* c, const ExpandArgs& a) {
-  bool ok = false;
+  int rc = PULL_OK;
   switch (c->words) {
-    case 1: ok = launch_expand_w<1>(c, a); break;
-    case 2: ok = launch_expand_w<2>(c, a); break;
-    case 4: ok = launch_expand_w<4>(c, a); break;
-    case 8: ok = launch_expand_w<8>(c, a); break;
-    case 16: ok = launch_expand_w<16>(c, a); break;
-    case 32: ok = launch_expand_w<32>(c, a); break;
-    case 64: ok = launch_expand_w<64>(c, a); break;
+    case 1: rc = launch_expand_w<1>(c, a); break;
+    case 2: rc = launch_expand_w<2>(c, a); break;
+    case 4: rc = launch_expand_w<4>(c, a); break;
+    case 8: rc = launch_expand_w<8>(c, a); break;
+    case 16: rc = launch_expand_w<16>(c, a); break;
+    case 32: rc = launch_expand_w<32>(c, a); break;
+    case 64: rc = launch_expand_w<64>(c, a); break;
     default: return set_error(GP_EINVAL, "unsupported word count");
   }
   GP_HIP(hipGetLastError());
-  if (!ok) return set_error(GP_EINVAL, "the round chose a pull kernel that is not built for this row width");
+  if (rc == PULL_ORDER_FAILED) return set_error(GP_EHIP, "the hub chunks could not be ordered against the round's pull kernel");
+  if (rc == PULL_NOT_BUILT) return set_error(GP_EINVAL, "the round chose a pull kernel that is not built for this row width");
   return 0;
 }
 

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "block_order.h"
 #include "gp_device.h"
 #include "xplan.h"
 
@@ -131,6 +132,23 @@ __global__ __launch_bounds__(BLOCK) void k_nbsum(const int64_t* __restrict__ rp,
 }
 
 
+// launch order of k_expand's blocks (block_order.h): the longest non-hub
+// in-list of a block decides, so the order follows the hub table wherever that
+// is rebuilt (partition, hub_threshold)
+// (cut: 1024 arcs is about 2 % of C4's blocks; C4 41.64-41.81 against 42.13-42.29
+// ms with the hub passes as before, 256 no better, a whole sort a little
+// worse: profiles/r08_ab_pull_schedule.txt)
+#ifndef GP_BLOCK_ORDER_CUT
+#define GP_BLOCK_ORDER_CUT 1024
+#endif
+static int build_block_order(Ctx* c) {
+  dfree(&c->d_border);
+  if (c->h_row_ptr.empty() || c->nloc() <= 0) return 0;
+  const std::vector<int32_t> order = block_order(c->h_row_ptr.data(), c->nloc(), c->cfg.hub_threshold, GP_BLOCK_ORDER_CUT);
+  GP_TRY(dalloc(&c->d_border, order.size()));
+  return copy_sync(c, c->d_border, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+}
+
 int build_hubs(Ctx* c) {
   c->h_hub_items.clear();
   std::vector<int32_t> hubs, ptr;
@@ -162,7 +180,7 @@ int build_hubs(Ctx* c) {
     GP_TRY(copy_sync(c, c->d_hubs, hubs.data(), hubs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   GP_TRY(copy_sync(c, c->d_hub_item_ptr, ptr.data(), ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   if (c->words > 0) GP_TRY(dalloc(&c->d_hub_partial, c->h_hub_items.size() * (size_t)c->words));
-  return 0;
+  return build_block_order(c);
 }
 
 static void free_state(Ctx* c);
@@ -496,7 +514,17 @@ int gp_create(int device, gp_ctx** out) {
     delete c;
     return set_error(GP_EHIP, "hipStreamCreate failed");
   }
+  // (a high-priority side stream measured the same, profiles/r08_ab_pull_schedule.txt)
+  if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess) {
+    gp_destroy(c);
+    return set_error(GP_EHIP, "hipStreamCreate failed");
+  }
   for (auto& e : c->ev) (void)hipEventCreate(&e);
+  if (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
+    gp_destroy(c);
+    return set_error(GP_EHIP, "hipEventCreate failed");
+  }
   if (dalloc(&c->d_stats, 64 + (size_t)NPART * NST) != 0) {
     gp_destroy(c);
     return GP_ENOMEM;
@@ -512,6 +540,7 @@ void gp_destroy(gp_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
+  if (c->side) (void)hipStreamSynchronize(c->side);
   if (c->comm) (void)ncclCommDestroy(c->comm);
   shard_free(c);
   dfree(&c->d_row_ptr); dfree(&c->d_col); dfree(&c->d_out_row_ptr); dfree(&c->d_out_col);
@@ -530,10 +559,13 @@ void gp_destroy(gp_ctx* c) {
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_stats);
   dfree(&c->d_hub_items); dfree(&c->d_hubs); dfree(&c->d_hub_item_ptr);
-  dfree(&c->d_hub_partial); dfree(&c->d_hub_pnz); dfree(&c->d_hub_done);
+  dfree(&c->d_hub_partial); dfree(&c->d_hub_pnz); dfree(&c->d_hub_done); dfree(&c->d_border);
   bitcount_free(c);
   if (c->h_stats) (void)hipHostFree(c->h_stats);
   for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
+  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+  if (c->side) (void)hipStreamDestroy(c->side);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
