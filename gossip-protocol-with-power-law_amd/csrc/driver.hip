@@ -636,6 +636,22 @@ static int launch_expand(Ctx* c) {
   // round holding every alive message of its component never receives again
   a.sate = alive_now(c) && c->early_exit_now && c->round >= c->last_inject_round ? 1 : 0;
   if (a.sate && c->sate_since < 0) c->sate_since = c->round;
+  // Complete lines of a top in-neighbour: the unfiltered
+  // early-exit pulls of k_expand<64> that read no receiver list (an aliased
+  // candidate of a done-probe round holds every line: no row is read), under
+  // alias_ok's conditions.  By default only where it paid: once the
+  // Message-Lists outgrow the Infinity Cache (n_alloc x 8W > 256 MiB: below
+  // that the dense rounds are not HBM-bound) and before the done-neighbour
+  // rounds (C4 round 3: 71.1 -> 47.6 GB of row bytes, 16.0 -> 14.5 ms; round
+  // 4's row bytes fell by 21 % too, but the round, which waits on the
+  // per-receiver chain, ran 0.07 ms slower: profiles/r09_ab_line_done.txt).
+  // GP_LINE_DONE=1 turns it on in every eligible round whatever the size,
+  // GP_LINE_DONE=0 off
+  const bool ld_big = (double)c->n_alloc * 8.0 * (double)c->words > 256.0 * 1024.0 * 1024.0;
+  c->line_done_now = alias_ok && c->early_exit_now && c->unfiltered_now && !c->mode_push &&
+                     !c->ulist_read_now && c->d_ldone != nullptr && c->n_ld_cand > 0 &&
+                     (c->ld_env < 0 ? ld_big && !c->dnb_now : c->ld_env == 1);
+  a.ldone = c->line_done_now ? c->d_ldone : nullptr;
   c->lines_ran = c->lines_from_commits = false;
   return launch_round_kernels(c, a);
 }

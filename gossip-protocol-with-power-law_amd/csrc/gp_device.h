@@ -220,6 +220,9 @@ struct ExpandArgs {
   int32_t hub_thr;
   const int32_t* __restrict__ border;  // k_expand (not SCAN_LIST): the block of 64 vertices the k-th wave
                                        //   takes, long in-lists first (block_order.h; null: block k)
+  const uint8_t* __restrict__ ldone;   // [n_alloc] early-exit pulls of big W = 64 runs without liveness: bit l =
+                                       //   line l of u's Message-List held every message of its component at
+                                       //   the start of the round (k_line_done; 0: not a candidate; else null)
 };
 
 constexpr uint8_t SLOT_NONE = 0xFF;
@@ -949,6 +952,7 @@ void launch_mklm(Ctx* c, const ExpandArgs& a);        // line masks of the sende
 void launch_arcmask(Ctx* c);                          // per-arc activity mask
 template <int W> void launch_fixup_rows_w(Ctx* c);    // unfiltered round: stale rows zeroed
 template <int W> void launch_park_w(Ctx* c);          // ... under liveness: crashed vertices' rows parked
+void launch_line_done(Ctx* c);                        // complete lines of the big vertices' Message-Lists (W = 64)
 // push.hip
 template <int W> void launch_push_w(Ctx* c, ExpandArgs a);            // a push round
 template <int W> void launch_split_push_w(Ctx* c, const ExpandArgs& a);   // degree-split round: the push half

@@ -279,6 +279,17 @@ struct Ctx {
   // [ceil(nloc / 64)] launch order of k_expand's blocks: the blocks with a long
   // non-hub in-list first (block_order.h; rebuilt with the hub table)
   int32_t* d_border = nullptr;
+  // per-line done-neighbour rule (line_cands.h): the owned
+  // vertices of in-degree >= ld_min_deg (rebuilt with the hub table), and a
+  // byte per vertex -- bit l: line l of its Message-List held every message of
+  // its component when k_line_done last ran; 0 for every non-candidate
+  int32_t* d_ld_cand = nullptr;
+  int64_t n_ld_cand = 0;
+  uint8_t* d_ldone = nullptr;       // [n_alloc], per-run state
+  size_t ldone_bytes = 0;           // its size as allocated
+  int32_t ld_env = -1;              // GP_LINE_DONE in the environment at gp_create: 0 off, 1 on, -1 by size
+  int32_t ld_min_deg = 0;           // GP_LINE_DONE_MIN_DEG there, else the compile-time default
+  bool line_done_now = false;       // this round's pull seeds its targets from d_ldone
 
   // rccl
   ncclComm_t comm = nullptr;

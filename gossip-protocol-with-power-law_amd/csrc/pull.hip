@@ -46,6 +46,12 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
   // ... and at W = 32 / 16 four / eight at a time (gather_groups; not at W = 8:
   // 16 receivers per step took 96 VGPRs and were slower, profiles/r06_ab_w8.txt)
   constexpr bool GGROUPS = (W == 32 || W == 16) && QUADS && !ALIVE && SCAN == SCAN_UNFILTERED && !LIST;
+  // the variants that take the complete lines of a top in-neighbour from
+  // their receivers' targets (a.ldone): the unfiltered
+  // early-exit pulls without liveness or list (C4 rounds 3 and 4, and the
+  // done-probe variant behind them, which keeps its 70 VGPRs); the other
+  // variants compile none of it
+  constexpr bool LDONE = W == 64 && !ALIVE && !LIST && SCAN == SCAN_UNFILTERED;
   WaveStats st;
   ws_zero<EWAVES>(st);
   // the wave's block of 64 vertices: the blocks with a long non-hub in-list are
@@ -155,6 +161,14 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
       // (with alive sets -- liveness -- only the SCAN_ALIVE variants: the done
       // target is then cmask & F_r & ~seen, which the others cannot form)
       if (a.dbits && need && (ALIVE || !a.alive)) dnb = done_nb(a, b, e);
+      if constexpr (LDONE) {
+        // complete lines of the first two in-neighbours, carried above the
+        // slot byte (a done in-neighbour already gives all four)
+        if (a.ldone && need && (!QUADS || small)) {   // (quads variant: gather_pairs' receivers only)
+          const uint32_t ld = line_done_nb(a, b, e);
+          if (!dnb) slot_of |= ld << LD_SHIFT;
+        }
+      }
     }
     if constexpr ((MODE & 3) == SCAN_PRE) st.add(S_ARCS, (u64)wave_sum_u32(pre_arcs));
     st.add(S_SENDS, wave_sum_u64(sends));
@@ -295,7 +309,8 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
       } else {
         ve = L.rp[k + 1];
       }
-      const uint32_t sv_slot = (uint32_t)__builtin_amdgcn_readlane((int)slot_of, k);
+      const uint32_t sv_raw = (uint32_t)__builtin_amdgcn_readlane((int)slot_of, k);
+      const uint32_t sv_slot = LDONE ? sv_raw & LD_SLOT_MASK : sv_raw;
       u64x2 acc = {0, 0}, want = {0, 0};
       // early-exit rounds: the first pass's column ids are loaded beside the
       // target's seen / component rows, one round trip instead of two
@@ -315,15 +330,33 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
         }
         if (sv_slot != SLOT_NONE) st.add(S_SEEN_READ, 1);
       }
+      bool covered = false;   // LDONE: the complete lines cover the whole target, nothing to scan
       if (ee) {
         if (sv_slot != SLOT_NONE) st.add(S_SEEN_READ, 1);
         want = early_exit_target<W, LDS_OF(MODE), ALIVE>(a, v, L, g, lw, sv_slot, L.mi[k]);
+        // (not in the quads variant: its receivers of in-degree <= 32 take the
+        // rule in gather_pairs, and here it cost 4 VGPRs and the seventh wave)
+        if constexpr (LDONE && !QUADS) {
+          // lines a top in-neighbour held whole: the receiver ends the round
+          // with all of cmask there whatever the others hold, so those words
+          // are gathered from nobody (gather_rows_n's `live` never loads them).
+          // The lanes come from a scalar mask: testing the lane's own line bit
+          // took 2 VGPRs and this variant's eighth wave
+          const uint32_t ld = sv_raw >> LD_SHIFT;
+          if (ld) {
+            if (__builtin_amdgcn_inverse_ballot_w64(line_lanes(ld))) acc = want;
+            const u64x2 rem = want & ~acc;
+            covered = !__any((rem.x | rem.y) != 0ull);
+          }
+        }
       }
       // (with alive sets a receiver may hold every alive message of its
       // component already: then there is nothing to scan)
       if (ALIVE && ee && a.alive && !__any((want.x | want.y) != 0ull)) {
         if (a.sate) sat |= 1ull << k;
-      } else if ((mdn >> k) & 1ull) {   // a done in-neighbour: its Message-List is the whole target
+      } else if (((mdn >> k) & 1ull) || covered) {
+        // a done in-neighbour: its Message-List is the whole target (covered:
+        // complete lines give the same, acc holds it already) -- nothing to scan
         acc = want;
       } else if constexpr ((MODE & 3) == SCAN_PRE) {
         const uint32_t np = L.np[k];
@@ -534,6 +567,8 @@ static int launch_expand_w(Ctx* c, ExpandArgs a) {
   }
   if (a.unfiltered && c->liveness_active) launch_park_w<W>(c);
   if (a.unfiltered) launch_fixup_rows_w<W>(c);
+  // (k_line_done reads the rows as they are now: after the last round's k_hub_final, before the fork)
+  if (a.ldone) launch_line_done(c);
   const PullChoice p = choose_pull(c, a, W);
   if (p.masked) launch_arcmask(c);
   // kernel_ms (ev[4] .. ev[5]) brackets every kernel of the round's pull: the

@@ -1,7 +1,8 @@
 // pull_aux.hip -- the helper passes around a pull round: line masks of the
 // senders (k_mklm), the per-arc activity mask (k_arcmask), aliased
 // Message-Lists back to rows (k_unalias), stale rows of an unfiltered round
-// (k_fixup_rows), parking of crashed vertices' rows (k_park); their launchers.
+// (k_fixup_rows), parking of crashed vertices' rows (k_park), the big vertices'
+// complete lines (k_line_done); their launchers.
 #include "gp_device.h"
 
 namespace gp {
@@ -190,6 +191,54 @@ __global__ __launch_bounds__(BLOCK) void k_park(const uint8_t* __restrict__ stat
       }
     }
   }
+}
+
+// Complete lines of the big vertices' Message-Lists (W = 64; DESIGN.md §3.3
+// "Complete lines of a top in-neighbour"): before an early-exit pull without
+// liveness, ldone[u] bit l = the 128-B line l of u's current row holds every
+// message of u's component on that line, for the candidates u (line_cands.h);
+// the pull's receivers probe the bytes of their first two in-neighbours.  A
+// half-wave per candidate: u's current Message-List, slot[sp[u]], against the
+// component row, 8 lanes per line.  The receivers gather S[r & 1][u], which
+// is that row only if u received last round and else an older or zeroed one;
+// the rule holds all the same by forward-once (gp_device.h, "expansion"):
+// every bit of u's Message-List outside its frontier was sent to v when u
+// first received it, so v already holds it, and the frontier is in the row v
+// gathers -- v ends the round with all of u's line whichever row it reads.  An aliased candidate holds its whole
+// component (0xF, no row read); no row, a parked row or no messages give 0.
+// Every candidate's byte is rewritten by every pass, every other byte stays 0.
+__global__ __launch_bounds__(BLOCK) void k_line_done(const int32_t* __restrict__ cand, int64_t ncand,
+                                                     const uint8_t* __restrict__ sp, const int32_t* __restrict__ midx,
+                                                     const u64* __restrict__ cmask, const u64* __restrict__ s0,
+                                                     const u64* __restrict__ s1, uint8_t* __restrict__ ldone) {
+  const int lane = threadIdx.x & 63, h = lane >> 5, lw = lane & 31;
+  const int64_t stride = (int64_t)gridDim.x * WAVES * 2;
+  for (int64_t p0 = ((int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6)) * 2; p0 < ncand; p0 += stride) {
+    const int64_t p = p0 + h;
+    const bool on = p < ncand;
+    const int32_t u = on ? cand[p] : 0;
+    const uint32_t s = on ? (uint32_t)sp[u] : (uint32_t)SLOT_NONE;
+    const int32_t k = on ? midx[u] : -1;
+    bool covered = false;   // this lane's two words hold every message of the component
+    if (s < 2u && k >= 0) {
+      const u64x2 row = load_piece<64>(s ? s1 : s0, u, lw);
+      const u64x2 lack = load_piece<64>(cmask, k, lw) & ~row;
+      covered = (lack.x | lack.y) == 0ull;
+    }
+    const uint32_t hb = (uint32_t)(__ballot(covered) >> (32 * h));
+    uint32_t l = 0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) l |= ((hb >> (8 * t)) & 0xFFu) == 0xFFu ? (1u << t) : 0u;
+    if (s == SLOT_CMASK && k >= 0) l = 0xFu;
+    if (on && lw == 0) ldone[u] = (uint8_t)l;
+  }
+}
+
+void launch_line_done(Ctx* c) {
+  if (c->n_ld_cand <= 0) return;
+  hipLaunchKernelGGL(k_line_done, dim3(std::min(grid_for(c->n_ld_cand, (int64_t)WAVES * 2), c->cu_count * 8 * GS)),
+                     dim3(BLOCK), 0, c->stream, c->d_ld_cand, c->n_ld_cand, c->d_sp, c->d_midx, c->d_cmask,
+                     c->d_slot[0], c->d_slot[1], c->d_ldone);
 }
 
 void launch_mklm(Ctx* c, const ExpandArgs& a) {

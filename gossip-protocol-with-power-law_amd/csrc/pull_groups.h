@@ -270,6 +270,35 @@ __device__ __forceinline__ bool done_nb(const ExpandArgs& a, int64_t b, int64_t 
   return d;
 }
 
+// Complete lines of a top in-neighbour (a.ldone rounds: early
+// exit, no liveness, one context, W = 64).  done_nb's argument per 128-B line:
+// if in-neighbour u held every message of the component on line l at the
+// start of the round, the OR over v's in-neighbours covers cmask there, every
+// Message-List is a subset of cmask, so v's new bits on line l are exactly
+// cmask_l & ~seen_l -- and line l of no row need be fetched, u's included.
+// k_line_done (pull_aux.hip) wrote the byte of every big vertex before the
+// round; probed like done_nb, for the same DNB_K arcs, all loads in flight.
+// The mask rides above the slot byte in the lane's slot_of.
+constexpr int LD_SHIFT = 8;
+constexpr uint32_t LD_SLOT_MASK = (1u << LD_SHIFT) - 1u;
+// the lanes of a wave whose 16-B pieces lie on the lines of mask l (W = 64: a
+// half-wave per row, 8 lanes per line); l wave-uniform: scalar code
+__device__ __forceinline__ u64 line_lanes(uint32_t l) {
+  u64 m = 0;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) m |= ((l >> t) & 1u) ? 0x000000FF000000FFull << (8 * t) : 0ull;
+  return m;
+}
+__device__ __forceinline__ uint32_t line_done_nb(const ExpandArgs& a, int64_t b, int64_t e) {
+  int32_t c[DNB_K];
+#pragma unroll
+  for (int q = 0; q < DNB_K; ++q) c[q] = b + q < e ? a.gcol[b + q] : -1;
+  uint32_t l = 0;
+#pragma unroll
+  for (int q = 0; q < DNB_K; ++q) l |= c[q] >= 0 ? (uint32_t)a.ldone[c[q]] : 0u;
+  return l & 0xFu;
+}
+
 // Receivers with a done in-neighbour two at a time, one per half-wave (W =
 // 64): nothing to gather, so each pair is one round trip (its seen rows and
 // the component rows, the latter L2-resident) and the commit
@@ -666,7 +695,10 @@ __device__ __forceinline__ u64 gather_pairs(const ExpandArgs& a, LDS& L, u64 mp,
     const int v = (int)(a.vbegin + base + ks);
     const int64_t vb = L.rp[ks];
     const int deg = on ? (int)(L.rp[ks + 1] - vb) : 0;   // <= 32 (the caller's mask)
-    const uint32_t sv_slot = (uint32_t)__shfl((int)slot_of, ks);
+    // the receiver's slot, with the complete lines of its top in-neighbours
+    // above it (line_done_nb; none: 0)
+    const uint32_t sv_raw = (uint32_t)__shfl((int)slot_of, ks);
+    const uint32_t sv_slot = sv_raw & LD_SLOT_MASK;
     u64x2 want = {0, 0};
     if (lw < deg) L.idx[32 * h + lw] = a.gcol[vb + lw];   // (this pair's column ids: half h at 32h)
     wave_sync_lds();
@@ -688,8 +720,11 @@ __device__ __forceinline__ u64 gather_pairs(const ExpandArgs& a, LDS& L, u64 mp,
     const uint32_t sB = (uint32_t)__builtin_amdgcn_readlane((int)sv_slot, 32);
     st.add(S_ARCS, (u64)(dA + dB));
     st.add(S_SEEN_READ, (u64)((sA != SLOT_NONE ? 1 : 0) + (kB >= 0 && sB != SLOT_NONE ? 1 : 0)));
-    bool live = on && (!ee || (want.x | want.y) != 0ull);   // this lane's words still miss messages
     u64x2 acc = {0, 0};
+    // (a complete line of a top in-neighbour: its words are the target, gathered from nobody)
+    if (on && ee && ((sv_raw >> LD_SHIFT >> (lw >> 3)) & 1u)) acc = want;
+    const u64x2 lack = want & ~acc;
+    bool live = on && (!ee || (lack.x | lack.y) != 0ull);   // this lane's words still miss messages
     u64 rows = 0, pieces = 0;
     for (int k0 = 0; k0 < max(dA, dB); k0 += GP_GPAIR_RIF) {
       const u64 lb = __ballot(live);

@@ -10,6 +10,7 @@
 
 #include "block_order.h"
 #include "gp_device.h"
+#include "line_cands.h"
 #include "xplan.h"
 
 namespace gp {
@@ -149,6 +150,22 @@ static int build_block_order(Ctx* c) {
   return copy_sync(c, c->d_border, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice);
 }
 
+// candidates of the per-line done-neighbour rule (line_cands.h), beside the
+// hub table.  The byte array is per-run state (alloc_state); a new list zeroes
+// it, so a vertex that stops being a candidate leaves no byte behind
+static int build_line_cands(Ctx* c) {
+  dfree(&c->d_ld_cand);
+  c->n_ld_cand = 0;
+  if (c->d_ldone) GP_HIP(hipMemsetAsync(c->d_ldone, 0, c->ldone_bytes, c->stream));
+  if (c->h_row_ptr.empty() || c->nloc() <= 0) return 0;
+  const std::vector<int32_t> cand = line_cands(c->h_row_ptr.data(), c->nloc(), c->ld_min_deg);
+  if (cand.empty()) return 0;
+  GP_TRY(dalloc(&c->d_ld_cand, cand.size()));
+  GP_TRY(copy_sync(c, c->d_ld_cand, cand.data(), cand.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  c->n_ld_cand = (int64_t)cand.size();
+  return 0;
+}
+
 int build_hubs(Ctx* c) {
   c->h_hub_items.clear();
   std::vector<int32_t> hubs, ptr;
@@ -180,6 +197,7 @@ int build_hubs(Ctx* c) {
     GP_TRY(copy_sync(c, c->d_hubs, hubs.data(), hubs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   GP_TRY(copy_sync(c, c->d_hub_item_ptr, ptr.data(), ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   if (c->words > 0) GP_TRY(dalloc(&c->d_hub_partial, c->h_hub_items.size() * (size_t)c->words));
+  GP_TRY(build_line_cands(c));
   return build_block_order(c);
 }
 
@@ -226,7 +244,7 @@ static void free_state(Ctx* c) {
     dfree(&c->d_frx[k]);
     dfree(&c->d_fpop[k]);
   }
-  dfree(&c->d_sp); dfree(&c->d_ws);
+  dfree(&c->d_sp); dfree(&c->d_ws); dfree(&c->d_ldone);
   dfree(&c->d_ulist[0]); dfree(&c->d_ulist[1]);
   c->ulist_valid = false;
   dfree(&c->d_seenpop); dfree(&c->d_first); dfree(&c->d_digest);
@@ -349,6 +367,12 @@ static int alloc_state(Ctx* c) {
   GP_TRY(dalloc(&c->d_det_base, (size_t)DET_CAP));
   GP_TRY(dalloc(&c->d_abits, (na + 63) / 64));
   GP_TRY(dalloc(&c->d_dbits, (na + 63) / 64));
+  dfree(&c->d_ldone);   // (W = 64 only; every non-candidate's byte stays 0, k_line_done rewrites the others)
+  if (c->words == 64) {
+    GP_TRY(dalloc(&c->d_ldone, na));
+    c->ldone_bytes = na;
+    GP_HIP(hipMemsetAsync(c->d_ldone, 0, na, c->stream));
+  }
   dfree(&c->d_lm);
   if (c->words == 64) GP_TRY(dalloc(&c->d_lm, (na + 1) / 2 + 32));
   for (int k = 0; k < 2; ++k) {
@@ -508,6 +532,15 @@ int gp_create(int device, gp_ctx** out) {
   gp_ctx* c = new gp_ctx();
   c->device = device;
   gp_default_config(&c->cfg);
+  // the per-line done-neighbour rule: GP_LINE_DONE=0 / 1
+  // forces it off / on whatever the overlay's size, GP_LINE_DONE_MIN_DEG=k
+  // sets the candidates' in-degree; both read once, here
+  c->ld_min_deg = GP_LINE_DONE_MIN_DEG;
+  if (const char* e = getenv("GP_LINE_DONE")) c->ld_env = e[0] == '1' ? 1 : e[0] == '0' ? 0 : -1;
+  if (const char* e = getenv("GP_LINE_DONE_MIN_DEG")) {
+    const long k = strtol(e, nullptr, 10);
+    if (k >= 1 && k <= INT32_MAX) c->ld_min_deg = (int32_t)k;
+  }
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->cu_count = prop.multiProcessorCount;
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -552,7 +585,7 @@ void gp_destroy(gp_ctx* c) {
   dfree(&c->d_slot[2]);
   free_rows(c);
   for (int k = 0; k < 2; ++k) { dfree(&c->d_frx[k]); dfree(&c->d_fpop[k]); }
-  dfree(&c->d_sp); dfree(&c->d_ws);
+  dfree(&c->d_sp); dfree(&c->d_ws); dfree(&c->d_ldone); dfree(&c->d_ld_cand);
   dfree(&c->d_ulist[0]); dfree(&c->d_ulist[1]);
   dfree(&c->d_seenpop); dfree(&c->d_first); dfree(&c->d_digest);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
