@@ -643,6 +643,16 @@ int gp_load_graph(gp_ctx* c, int64_t n, int64_t nnz, const int64_t* row_ptr, con
   if (directed) {
     if (out_row_ptr && out_col) {
       if (out_row_ptr[0] != 0 || out_row_ptr[n] != nnz) return set_error(GP_EINVAL, "out CSR inconsistent");
+      for (int64_t v = 0; v < n; ++v)
+        if (out_row_ptr[v + 1] < out_row_ptr[v]) return set_error(GP_EINVAL, "out_row_ptr not monotone");
+      for (int64_t j = 0; j < nnz; ++j)
+        if (out_col[j] < 0 || out_col[j] >= n) return set_error(GP_EINVAL, "out_col index out of range");
+      // every vertex sends on as many arcs as in-lists name it
+      std::vector<int64_t> sent((size_t)n, 0);
+      for (int64_t j = 0; j < nnz; ++j) sent[(size_t)col[j]]++;
+      for (int64_t v = 0; v < n; ++v)
+        if (out_row_ptr[v + 1] - out_row_ptr[v] != sent[(size_t)v])
+          return set_error(GP_EINVAL, "out CSR degrees differ from the in-CSR's");
       orp.assign(out_row_ptr, out_row_ptr + n + 1);
       ocol.assign(out_col, out_col + nnz);
     } else {   // transpose the in-CSR: out(u) = {v : u in In(v)}

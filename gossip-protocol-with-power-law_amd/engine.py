@@ -62,11 +62,22 @@ class GossipEngine:
         check(self._lib.gp_configure(self._ctx, ctypes.byref(self.cfg)))
 
     # -- overlay -----------------------------------------------------------
-    def load_graph(self, csr):
+    def load_graph(self, csr, out_csr=None):
+        """out_csr=(out_row_ptr, out_col): the out-CSR of a directed overlay
+        (the transpose of csr, rows in any order); None lets gp_load_graph
+        transpose the in-CSR itself."""
         rp = np.ascontiguousarray(csr.row_ptr, dtype=np.int64)
         col = np.ascontiguousarray(csr.col, dtype=np.int32)
+        orp = ocol = None
+        if out_csr is not None:
+            if not csr.directed:
+                raise ValueError("an out-CSR goes with a directed overlay")
+            orp = np.ascontiguousarray(out_csr[0], dtype=np.int64)
+            ocol = np.ascontiguousarray(out_csr[1], dtype=np.int32)
+            if orp.shape != rp.shape or ocol.shape != col.shape:
+                raise ValueError("out-CSR and in-CSR differ in size")
         check(self._lib.gp_load_graph(self._ctx, int(csr.n), int(col.size), _ptr(rp), _ptr(col),
-                                      1 if csr.directed else 0, None, None))
+                                      1 if csr.directed else 0, _ptr(orp), _ptr(ocol)))
         self.n = int(csr.n)
 
     def build_chung_lu(self, n, dbar, gamma, seed):

@@ -203,7 +203,10 @@ int gp_configure(gp_ctx* ctx, const gp_config* cfg);
  * be NULL for undirected graphs (= in-degree).  For directed graphs the out-CSR
  * (out_row_ptr/out_col, may be NULL when directed == 0) gives the other side of
  * every heartbeat link for liveness reports (Peer.py:369-392 covers outgoing and
- * incoming connections). */
+ * incoming connections).  A NULL out-CSR of a directed graph is built by
+ * transposing the in-CSR; a given one must be its transpose (rows in any
+ * order): row_ptr monotone, ids in range and every vertex's out-degree equal
+ * to its count in col are checked, GP_EINVAL otherwise. */
 int gp_load_graph(gp_ctx* ctx, int64_t n, int64_t nnz, const int64_t* row_ptr,
                   const int32_t* col, int32_t directed, const int64_t* out_row_ptr,
                   const int32_t* out_col);
