@@ -136,6 +136,8 @@ SIGNATURES = {
     "gp_shard_host_init": (ctypes.c_int, [_P, AllGatherFn, _P, _I32, _I32]),
     "gp_shard_info": (ctypes.c_int, [_P, _PI32, _PI32, _PI32]),
     "gp_shard_combine": (ctypes.c_int, [_P, ctypes.POINTER(RoundStats), _I32, _PI32, ctypes.POINTER(ctypes.c_double)]),
+    "gp_track_curve": (ctypes.c_int, [_P, _I32]),
+    "gp_read_curve": (ctypes.c_int, [_P, _I32, _P, _I32, _PI32]),
     "gp_checkpoint_size": (ctypes.c_int, [_P, _PI64]),
     "gp_checkpoint_save": (ctypes.c_int, [_P, _P, _I64]),
     "gp_checkpoint_load": (ctypes.c_int, [_P, _P, _I64]),

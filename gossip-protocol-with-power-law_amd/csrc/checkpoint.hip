@@ -175,8 +175,9 @@ int gp_checkpoint_load(gp_ctx* c, const void* host, int64_t bytes) {
     return set_error(GP_EINVAL, "checkpoint of another overlay or message set");
   if (h.n_alloc != c->n_alloc || h.vbegin != c->vbegin || h.vend != c->vend)
     return set_error(GP_EINVAL, "checkpoint of another partition");
-  if (h.has_first != (c->cfg.track_first ? 1 : 0) || h.has_frx != (c->cfg.track_msg_forwards || c->local ? 1 : 0))
-    return set_error(GP_EINVAL, "checkpoint tracks other outputs (track_first / track_msg_forwards)");
+  if (h.has_first != (c->cfg.track_first ? 1 : 0) || h.has_frx != (c->holds_frx() ? 1 : 0))
+    return set_error(GP_EINVAL, "checkpoint tracks other outputs (track_first / frontier rows: track_msg_forwards, "
+                                "gp_track_curve)");
   GP_HIP(hipSetDevice(c->device));
   // the component targets (cmask rows) of this message set; computing them
   // touches no run state that could be in progress (set_messages invalidated it)
@@ -238,6 +239,9 @@ int gp_checkpoint_load(gp_ctx* c, const void* host, int64_t bytes) {
   c->cml_written_prev = false;   // compact lists are rebuilt by the next sparse round
   c->cml_read_now = c->cml_write_now = false;
   c->last_reports = h.last_reports;
+  // the spread curve is not in the blob (as the job record): a
+  // run restored at round 0 has counted nothing yet and keeps the cleared one
+  if (h.round > 0) c->curve_valid = false;
   return 0;
 }
 

@@ -683,6 +683,16 @@ static int launch_bitsum(Ctx* c, BitsumArgs a, bool cnt, bool sum) {
   return 0;
 }
 
+// the per-bit count of guarded rows, for curve.hip's yardstick (GP_CURVE_YARDSTICK)
+int bitsum_count_rows(Ctx* c, const u64* rows, const uint32_t* guard, int64_t count, u64* cnt) {
+  BitsumArgs b{};
+  b.rows = rows;
+  b.guard = guard;
+  b.cnt = cnt;
+  b.count = count;
+  return launch_bitsum(c, b, true, false);
+}
+
 // phases L_r, I_r, E_r of one round on one context (no host sync)
 static int round_launch(Ctx* c) {
   if (!state_ready(c) || c->words <= 0) return set_error(GP_ESTATE, "gp_set_messages + gp_reset first");
@@ -760,8 +770,7 @@ static int round_launch(Ctx* c) {
   hipLaunchKernelGGL(k_stats_reduce, dim3(NST), dim3(BLOCK), 0, s, partial, stats);
   GP_HIP(hipGetLastError());
   GP_HIP(hipEventRecord(c->ev[2], s));
-
-  return 0;
+  return curve_count_round(c);   // (nothing is launched unless gp_track_curve is on)
 }
 
 // X_r over RCCL.  One rank: the counters' all-reduce is the whole exchange.

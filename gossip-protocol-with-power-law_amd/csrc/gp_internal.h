@@ -136,8 +136,18 @@ struct Ctx {
   bool park_failed = false;         // slot 2 could not be allocated: no unfiltered pull under liveness
   uint8_t* d_sp = nullptr;          // [n_alloc] slot of v's seen row (0xFF: none)
   uint8_t* d_ws = nullptr;          // [n_alloc] bit p: slot p written this run
-  u64* d_frx[2] = {nullptr, nullptr};     // exact frontier rows (track_msg_forwards; partitioned)
+  u64* d_frx[2] = {nullptr, nullptr};     // exact frontier rows (track_msg_forwards; partitioned; spread curve)
   int64_t frx_rows = 0;                   // rows d_frx covers (partitioned: the owned ones)
+  // spread curve (curve.hip): [255][W * 64] first receipts per
+  // receipt round and message over the owned vertices.  curve_want is what
+  // gp_track_curve asked for, curve_alloc what alloc_state made, curve_on what
+  // the run since the last gp_reset counts; curve_valid falls when a
+  // checkpoint restores the run past round 0 (the curve is not in the blob)
+  u64* d_curve = nullptr;
+  bool curve_want = false, curve_alloc = false, curve_on = false, curve_valid = false;
+  int curve_grid = 0;                     // GP_CURVE_GRID at gp_create: cap of k_curve's grid (0: none)
+  bool curve_yard = false;                // GP_CURVE_YARDSTICK=1 at gp_create: time k_curve beside k_bitsum
+  bool holds_frx() const { return cfg.track_msg_forwards != 0 || local || curve_want; }
   uint32_t* d_fpop[2] = {nullptr, nullptr};    // [n_alloc]
   int cur = 0;
   uint32_t* d_seenpop = nullptr;    // [nloc]
@@ -314,6 +324,10 @@ struct Ctx {
   u64* d_jcf = nullptr;                 // [2][jm] the job's coverage, forwards
   int32_t jm = 0;                       // messages of the job
   bool j_ready = false, j_fwd_valid = false, j_dig_valid = false;
+  u64* d_jcurve = nullptr;              // [j_curve_rows][jm] the job's spread curve
+  size_t jcurve_words = 0;
+  int32_t j_curve_rows = 0;
+  bool j_curve_valid = false;           // every rank tracked a valid curve
 
   // kernel geometry
   int cu_count = 256;
@@ -374,6 +388,14 @@ int build_hubs(Ctx* c);
 int bitcount_messages(Ctx* c, bool weighted, u64* cov, u64* fwd);   // coverage / forwards of the owned rows
 int finalize_by_components(Ctx* c, bool weighted, u64* cov, u64* fwd);   // the same via cmask rows
 void bitcount_free(Ctx* c);
+// curve.hip
+int curve_alloc(Ctx* c, bool on);              // with the run state: the count buffer (or none)
+int curve_reset(Ctx* c);                       // new run: cleared, counted from here on
+int curve_count_round(Ctx* c);                 // after E_r: rows r (injections) and r + 1 (first receipts)
+int curve_env_grid();                          // GP_CURVE_GRID in the environment (0: unset)
+bool curve_env_yardstick();                    // GP_CURVE_YARDSTICK=1 in the environment
+// driver.hip: cnt[m] += the rows' bit m over rows [0, count) with guard[i] != 0 (the per-bit k_bitsum)
+int bitsum_count_rows(Ctx* c, const u64* rows, const uint32_t* guard, int64_t count, u64* cnt);
 // partition.hip
 int localize(Ctx* c);                          // global overlay -> owned + ghost local CSR, boundary lists
 int set_extras(Ctx* c, const std::vector<int32_t>& origins_global);   // origins neither owned nor ghosts

@@ -248,6 +248,8 @@ static void free_state(Ctx* c) {
   dfree(&c->d_ulist[0]); dfree(&c->d_ulist[1]);
   c->ulist_valid = false;
   dfree(&c->d_seenpop); dfree(&c->d_first); dfree(&c->d_digest);
+  (void)curve_alloc(c, false);
+  c->curve_on = false;
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_abits); dfree(&c->d_dbits); dfree(&c->d_lm); dfree(&c->d_lmw[0]); dfree(&c->d_lmw[1]); dfree(&c->d_sbits); dfree(&c->d_amask); dfree(&c->d_cml[0]); dfree(&c->d_cml[1]); dfree(&c->d_cmk[0]); dfree(&c->d_cmk[1]); dfree(&c->d_done_at);
@@ -335,8 +337,8 @@ static int alloc_state(Ctx* c) {
   // exact frontier rows only for per-message forwards (the pull reads whole
   // Message-Lists) and for the boundary exchange of a vertex
   // partition, which sends owned vertices' new bits: the owned rows only (a
-  // ghost's slot row is its frontier)
-  c->frx_rows = c->local ? c->nloc() : (c->cfg.track_msg_forwards ? c->n_alloc : 0);
+  // ghost's slot row is its frontier); the spread curve counts them too
+  c->frx_rows = c->local ? c->nloc() : (c->cfg.track_msg_forwards || c->curve_want ? c->n_alloc : 0);
   dfree(&c->d_slot[2]);   // (re)allocated at the first parking, for this W
   c->park_failed = false;
   // S[0] | S[1] | accumulator rows of the owned receivers, one allocation
@@ -410,6 +412,7 @@ static int alloc_state(Ctx* c) {
   GP_TRY(dalloc(&c->d_reports, (size_t)c->report_cap));
   GP_TRY(dalloc(&c->d_hub_partial, std::max<size_t>(c->h_hub_items.size(), 1) * W));
   if (c->local) GP_TRY(alloc_exchange(c));
+  GP_TRY(curve_alloc(c, c->curve_want));
   GP_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -541,6 +544,8 @@ int gp_create(int device, gp_ctx** out) {
     const long k = strtol(e, nullptr, 10);
     if (k >= 1 && k <= INT32_MAX) c->ld_min_deg = (int32_t)k;
   }
+  c->curve_grid = curve_env_grid();   // (a test lever, as GP_FINALIZE_ROWS: few blocks fill k_curve's planes)
+  c->curve_yard = curve_env_yardstick();
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->cu_count = prop.multiProcessorCount;
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -587,7 +592,7 @@ void gp_destroy(gp_ctx* c) {
   for (int k = 0; k < 2; ++k) { dfree(&c->d_frx[k]); dfree(&c->d_fpop[k]); }
   dfree(&c->d_sp); dfree(&c->d_ws); dfree(&c->d_ldone); dfree(&c->d_ld_cand);
   dfree(&c->d_ulist[0]); dfree(&c->d_ulist[1]);
-  dfree(&c->d_seenpop); dfree(&c->d_first); dfree(&c->d_digest);
+  dfree(&c->d_seenpop); dfree(&c->d_first); dfree(&c->d_digest); dfree(&c->d_curve);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_stats);
@@ -854,8 +859,9 @@ int gp_spread_keys(gp_ctx* c, int32_t hops, int32_t m, const int32_t* origin, ui
 
 int gp_reset(gp_ctx* c) {
   if (!c) return set_error(GP_EINVAL, "null ctx");
-  if (!state_ready(c)) GP_TRY(alloc_state(c));
   GP_HIP(hipSetDevice(c->device));
+  // (gp_track_curve takes effect here: frontier rows and the count buffer)
+  if (!state_ready(c) || c->curve_alloc != c->curve_want) GP_TRY(alloc_state(c));
   if (!c->done_at_valid) {
     GP_TRY(compute_done_at(c, c->n_groups));
     c->done_at_valid = true;
@@ -902,6 +908,7 @@ int gp_reset(gp_ctx* c) {
   c->alias_active = c->alias_now = c->dprobe_now = false;
   c->ulist_valid = c->ulist_emit_now = c->ulist_read_now = false;
   shard_reset(c);
+  GP_TRY(curve_reset(c));
   GP_HIP(hipStreamSynchronize(s));
   return 0;
 }

@@ -180,6 +180,8 @@ void shard_free(Ctx* c) {
   dfree(&c->d_jdig);
   c->jdig_words = 0;
   dfree(&c->d_jcf);
+  dfree(&c->d_jcurve);
+  c->jcurve_words = 0;
   shard_reset(c);
 }
 
@@ -281,8 +283,8 @@ void pack_stats(const gp_round_stats& s, u64* f) {
 
 // header words all-gathered first: every rank validates every rank's shape
 enum { H_N, H_NNZ, H_M, H_WORDS, H_WBASE, H_ROUNDS, H_DIGEST, H_FWD, H_CHURN, H_SEED, H_PFAIL, H_DIRECTED, H_OK,
-       H_CAP, NH = 16 };
-static_assert(H_CAP < NH, "header words");
+       H_CAP, H_CURVE, NH = 16 };   // H_CURVE: the rank tracks a spread curve and it is valid (curve.hip)
+static_assert(H_CURVE < NH, "header words");
 
 // (a failed growth keeps the scratch there was: the combine still needs its
 // first words to tell the other ranks)
@@ -323,6 +325,8 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
   hdr[H_DIRECTED] = (u64)c->directed;
   hdr[H_OK] = why.empty() ? 1 : 0;
   hdr[H_CAP] = (u64)cap;
+  hdr[H_CURVE] = c->curve_on && c->curve_valid ? 1 : 0;
+  c->j_curve_valid = false;
   GP_TRY(copy_sync(c, c->d_jscr, hdr.data(), NH * 8, hipMemcpyHostToDevice));
   GP_TRY(x.allgather(c->d_jscr, c->d_jscr + NH, NH));
   GP_TRY(copy_sync(c, all.data(), c->d_jscr + NH, all.size() * 8, hipMemcpyDeviceToHost));
@@ -372,7 +376,14 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
   const size_t o_st = 0, o_sta = o_st + (size_t)R * NF, o_cnt = o_sta + (size_t)P * R * NF,
                o_cnta = o_cnt + NB, o_bs = o_cnta + (size_t)P * NB, o_br = o_bs + (size_t)P * NB * L,
                o_dr = o_br + (size_t)P * NB * L, o_ds = o_dr + (size_t)P * Ld, o_cf = o_ds + Ld,
-               o_cfa = o_cf + 2 * MS, total = o_cfa + (size_t)P * 2 * MS;
+               o_cfa = o_cf + 2 * MS, o_cv = o_cfa + (size_t)P * 2 * MS;
+  // the spread curve (curve.hip): the job has one only if every rank tracked a
+  // valid one -- every rank reads the same words, so all take the same branch.
+  // [curve: CR*MS + P*CR*MS], CR = R + 1 receipt rounds, ranks' rows zero-padded
+  bool curve = true;
+  for (int q = 0; q < P; ++q) curve = curve && H(q, H_CURVE) != 0;
+  const size_t CR = (size_t)R + 1;
+  const size_t o_cva = o_cv + (curve ? CR * MS : 0), total = o_cva + (curve ? (size_t)P * CR * MS : 0);
   // Every allocation of the combine happens here, and the ranks exchange how
   // it went: a rank out of memory fails the job on every rank instead of
   // leaving its peers in the collectives below.
@@ -388,6 +399,11 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
       c->jm = 0;
       rc = dalloc(&c->d_jcf, 2 * (size_t)std::max<int64_t>(mt, 1));
       if (rc == 0) c->jm = (int32_t)mt;
+    }
+    if (rc == 0 && curve && c->jcurve_words < CR * (size_t)std::max<int64_t>(mt, 1)) {
+      c->jcurve_words = 0;
+      rc = dalloc(&c->d_jcurve, CR * (size_t)std::max<int64_t>(mt, 1));
+      if (rc == 0) c->jcurve_words = CR * (size_t)std::max<int64_t>(mt, 1);
     }
     const std::string err = rc ? gp_last_error() : "";
     const u64 ok = rc == 0 ? 1 : 0;
@@ -454,6 +470,21 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
                               hipMemcpyDeviceToDevice, s));
     }
   }
+
+  // 6. spread curves: each rank's columns at its block of the job table, row by
+  // row; ranks that ran fewer rounds hold zero rows past their own
+  if (curve) {
+    const size_t MM = (size_t)c->words * 64;
+    GP_HIP(hipMemsetAsync(S + o_cv, 0, CR * MS * 8, s));
+    GP_HIP(hipMemcpy2DAsync(S + o_cv, MS * 8, c->d_curve, MM * 8, (size_t)c->m * 8, (size_t)own + 1,
+                            hipMemcpyDeviceToDevice, s));
+    GP_TRY(x.allgather(S + o_cv, S + o_cva, CR * MS));
+    for (int q = 0; q < P; ++q) {
+      const size_t at = (size_t)H(q, H_WBASE) * 64, mq = (size_t)H(q, H_M);
+      GP_HIP(hipMemcpy2DAsync(c->d_jcurve + at, (size_t)mt * 8, S + o_cva + (size_t)q * CR * MS, MS * 8, mq * 8, CR,
+                              hipMemcpyDeviceToDevice, s));
+    }
+  }
   GP_HIP(hipEventRecord(c->ev[5], s));
   std::vector<u64> cnta((size_t)P * NB);
   GP_HIP(hipMemcpyAsync(sta.data(), S + o_sta, sta.size() * 8, hipMemcpyDeviceToHost, s));
@@ -501,6 +532,8 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
   c->jm = (int32_t)mt;
   c->j_fwd_valid = fwd;
   c->j_dig_valid = dig;
+  c->j_curve_valid = curve;
+  c->j_curve_rows = (int32_t)CR;
   c->j_ready = true;
   if (rounds_out) *rounds_out = R;
   if (ms_out) {

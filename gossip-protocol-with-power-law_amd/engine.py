@@ -370,6 +370,30 @@ class GossipEngine:
     def forwards(self):
         return self._read(_lib.FORWARDS, np.empty(self.m, dtype=np.uint64))
 
+    # -- spread curves (csrc/curve.hip; helpers in spread.py) ----------------
+    def track_curve(self, on=True):
+        """gp_track_curve: count first receipts per (receipt round, message)
+        from the next reset() on."""
+        check(self._lib.gp_track_curve(self._ctx, 1 if on else 0))
+
+    def _read_curve(self, job, m):
+        buf = np.zeros((255, int(m)), dtype=np.uint64)   # receipt rounds 0 .. 254
+        rows = ctypes.c_int32()
+        check(self._lib.gp_read_curve(self._ctx, job, _ptr(buf), buf.shape[0], ctypes.byref(rows)))
+        return buf[:rows.value].copy()
+
+    def curve(self):
+        """u64 [rounds run + 1][m]: curve[r][k] = owned vertices whose first
+        receipt of message k has receipt round r (an origin's own receipt at
+        its inject round included) -- the column histograms of first().  With
+        spread_order's permutation p the columns are those of message p[k], as
+        for coverage()."""
+        return self._read_curve(0, self.m)
+
+    def job_curve(self, m_total):
+        """The whole shard job's curve after combine(): u64 [job rounds + 1][m_total]."""
+        return self._read_curve(1, m_total)
+
     def _nv(self):   # per-vertex reads: the owned slice of a partitioned context
         return self.nloc() if self.nranks > 1 else self.n
 

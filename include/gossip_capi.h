@@ -292,6 +292,33 @@ int gp_shard_info(gp_ctx* ctx, int32_t* nranks_out, int32_t* rank_out, int32_t* 
  * *ms_out (may be NULL) = device time of the combine on the engine stream. */
 int gp_shard_combine(gp_ctx* ctx, gp_round_stats* job, int32_t cap, int32_t* rounds_out, double* ms_out);
 
+/* Spread curves: curve[r][k] = the vertices whose first receipt of message k
+ * has receipt round r -- column by column the histogram of the first-receipt
+ * matrix (GP_FIRST), kept at sizes where that matrix cannot be (DESIGN.md
+ * §3.7).  It is the aggregate of what each reference peer logs per arrival
+ * (Peer.py:175-216: every received gossip with its time).  An origin's own
+ * receipt at its inject round counts; a lost message counts nowhere; a vertex-
+ * partitioned context counts its owned vertices, as GP_COVERAGE does.
+ *
+ * gp_track_curve(on) takes effect at the next gp_reset, which makes the
+ * allocations: the exact frontier rows (2 x n x 8W bytes, as with
+ * track_msg_forwards) and a [255][64W] u64 count buffer.  Tracking adds a
+ * counting pass after each round's expansion (round_ms carries it; expand_ms
+ * and kernel_ms keep their meaning); it changes no other output and makes
+ * neither GP_FRONTIER nor GP_FORWARDS readable where they were not.
+ *
+ * gp_read_curve writes u64 [rows][m] (the m real columns) and *rows_out = rows.
+ * job = 0: this context's curve, rows = rounds run since gp_reset + 1; row R
+ * holds the receipts round R-1's expansion produced (round R's injections are
+ * not made yet).  GP_ENOTRACK before tracking took effect; GP_ESTATE for a run
+ * restored from a checkpoint past round 0 (the blob does not hold the curve),
+ * until the next gp_reset.  job = 1: the whole shard job's curve after
+ * gp_shard_combine (else GP_ESTATE), the ranks' curves at their blocks of the
+ * job's message order, rows = the job's rounds + 1; GP_ENOTRACK unless every
+ * rank tracked a valid curve.  GP_EINVAL if cap_rows < rows: nothing is written. */
+int gp_track_curve(gp_ctx* ctx, int32_t on);
+int gp_read_curve(gp_ctx* ctx, int32_t job, uint64_t* host, int32_t cap_rows, int32_t* rows_out);
+
 /* Checkpoints (no reference counterpart -- the
  * reference's peers keep no state across restarts).  Taken between rounds:
  * the blob holds the whole per-run state of this context (Message-List rows in
