@@ -652,6 +652,16 @@ static int launch_expand(Ctx* c) {
                      !c->ulist_read_now && c->d_ldone != nullptr && c->n_ld_cand > 0 &&
                      (c->ld_env < 0 ? ld_big && !c->dnb_now : c->ld_env == 1);
   a.ldone = c->line_done_now ? c->d_ldone : nullptr;
+  // The packed gather: the same pulls -- k_expand<64>'s
+  // unfiltered early-exit rounds without liveness, receiver list or done
+  // probe.  By default under the per-line rule's size gate (the live lines
+  // collapse to one under the spread order at W = 64, and nothing was measured
+  // below that size) and before the done-neighbour rounds (the plain variant,
+  // C4 round 3).  GP_LINE_PACK=1 turns it on in every eligible round whatever
+  // the size, GP_LINE_PACK=0 off
+  c->line_pack_now = alias_ok && c->early_exit_now && c->unfiltered_now && !c->mode_push &&
+                     !c->ulist_read_now && !c->dprobe_now &&
+                     (c->lp_env < 0 ? ld_big && !c->dnb_now : c->lp_env == 1);
   c->lines_ran = c->lines_from_commits = false;
   return launch_round_kernels(c, a);
 }

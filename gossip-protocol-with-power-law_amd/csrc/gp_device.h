@@ -11,6 +11,7 @@
 #include <cstdint>
 
 #include "gp_internal.h"
+#include "line_pack.h"
 
 namespace gp {
 
@@ -287,8 +288,17 @@ constexpr int PRE_MAX_DEG = 16;  // in-degree up to which the lane phase probes
 #define GP_WAVE_PRE_MAX 64
 #endif
 constexpr int WAVE_PRE_N = 4;   // (2 and 8 measured equal)
-template <bool PRE, bool CML, bool LIST = false, bool PAIRS = false>
-struct WaveLdsT {
+// SCAN_PACK: the receiver's row-layout state, parked while the lanes hold
+// packed lines (an empty base elsewhere: the other variants' LDS is unchanged)
+template <bool PACK>
+struct PackLds {};
+template <>
+struct PackLds<true> {
+  u64 pa[64];   // the gathered OR so far (row slots reduced)
+  u64 pw[64];   // the early-exit target
+};
+template <bool PRE, bool CML, bool LIST = false, bool PAIRS = false, bool PACK = false>
+struct WaveLdsT : PackLds<PACK> {
   static constexpr bool kPre = PRE, kCml = CML, kList = LIST;
   u64 seen[PAIRS ? 128 : 64];   // early exit: the receiver's seen row (read once, reused by finish_row; gather_pairs: two)
   int32_t idx[64];      // active neighbours of one pass
@@ -309,7 +319,8 @@ struct WaveLdsT {
 };
 using WaveLds = WaveLdsT<false, false>;
 #define LDS_OF(MODE) \
-  WaveLdsT<((MODE) & 3) == SCAN_PRE, ((MODE) & SCAN_CML) != 0, ((MODE) & SCAN_LIST) != 0, ((MODE) & SCAN_QUADS) != 0>
+  WaveLdsT<((MODE) & 3) == SCAN_PRE, ((MODE) & SCAN_CML) != 0, ((MODE) & SCAN_LIST) != 0, ((MODE) & SCAN_QUADS) != 0, \
+           ((MODE) & SCAN_PACK) != 0>
 
 __device__ __forceinline__ void wave_sync_lds() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -419,7 +430,12 @@ enum ScanMode { SCAN_FILTERED = 0, SCAN_MASKED = 1, SCAN_UNFILTERED = 2, SCAN_PR
                                     (gather_pairs): the first aliasing round, near-done pulls,
                                     alive pulls from the half-held round; W = 32 / 16 / 8
                                     near-done pulls: low in-degree receivers 4 / 8 / 16 per step
-                                    (gather_groups) */ };
+                                    (gather_groups) */,
+                SCAN_PACK = 512 /* flag (k_expand, W = 64, unfiltered early-exit pulls without liveness,
+                                   list or done probe): the serial loop's row gather deals its lanes
+                                   out over the lines the receiver still misses (gather_rows_pack);
+                                   a variant of its own: 1 KB of LDS per wave, and the other
+                                   variants keep their code */ };
 
 // activity bits of arcs [j0, j0 + n) (n <= 64) from the per-arc mask, bit t =
 // arc j0 + t; j0 wave-uniform, so both words come in through scalar loads
@@ -547,6 +563,113 @@ __device__ __forceinline__ bool gather_rows(const ExpandArgs& a, const int32_t* 
   return gather_rows_n<W, RowsInFlight<W>::value>(a, idx, cnt, g, lw, acc, st, ee, want);
 }
 
+// The packed gather (SCAN_PACK; W = 64 early-exit pulls).
+// gather_rows_n keeps 32 lanes per row to the end, two rows per
+// wave-instruction, however few of a row's four lines are still fetched; under
+// the spread order a receiver soon misses messages on one or two lines only.
+// Here the wave takes the mask of the lines that still have a `live` lane
+// before the first batch and after every batch.  With three or four the batch
+// is gather_rows_n's.  With two a 16-lane group holds both lines of one
+// sender's row, with one an octet holds that line (line_pack.h): four or
+// eight rows per wave-instruction, the same lines fetched, a quarter to half
+// of the dependent round trips.  Lines only complete, so a receiver moves
+// 4 -> 2 -> 1 and never back.
+// One loop for every layout: acc and want are the lane's piece pp of the
+// gathered OR and of the target in the current layout (the row layout's
+// registers, no second set).  At a change of layout the lanes of row slot 0
+// park their pieces in LDS (the target once: it does not change) and every
+// lane takes the pieces of its new place; at the end the row layout comes
+// back the same way.  The accumulator is OR-reduced over the row slots before
+// every early-exit test, in place.  OR is idempotent and a dead line is
+// complete, so acc & ~seen is bit for bit gather_rows_n's.  All of it is
+// wave-uniform control flow: every lane is active in every shuffle.
+// packed wave-instructions in flight per batch, at most the row layout's (2:
+// C4 round 3 14.4 ms against 13.9 with 3 and the parent's 14.6,
+// profiles/r11_ab_line_pack.txt).  The layout is a run-time value on purpose:
+// a compile-time batch per layout took 94 VGPRs against 70
+#ifndef GP_PACK_RIF
+#define GP_PACK_RIF 3
+#endif
+template <class LDS>
+__device__ __forceinline__ bool gather_rows_pack(const ExpandArgs& a, LDS& L, const int32_t* idx, int cnt, int g,
+                                                 int lw, u64x2& acc, WaveStats& st, u64x2& want) {
+  constexpr int RIF = RowsInFlight<64>::value;
+  static_assert(GP_PACK_RIF >= 1 && GP_PACK_RIF <= RIF, "the packed batch reuses the row batch's registers");
+  const int lane = threadIdx.x & 63;
+  int sh = 5, pp = lw;   // log2 of the lanes per row, and this lane's piece of it
+  reduce_slots<64>(acc);
+  bool live;   // this lane's words still miss messages
+  {
+    const u64x2 miss = want & ~acc;
+    live = (miss.x | miss.y) != 0ull;
+  }
+  uint32_t lm = lines_of((uint32_t)__ballot(live));   // (both row slots hold the same target)
+  bool done = lm == 0u;
+  for (int k0 = 0; !done && k0 < cnt;) {
+    const int nsh = lp_row_shift(lm);
+    if (nsh != sh) {   // fewer live lines: deal the lanes out again
+      if (sh == 5 && g == 0) {
+        L.pw[2 * lw] = want.x;
+        L.pw[2 * lw + 1] = want.y;
+      }
+      if ((lane >> sh) == 0) {
+        L.pa[2 * pp] = acc.x;
+        L.pa[2 * pp + 1] = acc.y;
+      }
+      wave_sync_lds();
+      sh = nsh;
+      pp = lp_piece(lm, lane);   // (never -1: every lane of a packed layout lies on a live line)
+      acc = u64x2{L.pa[2 * pp], L.pa[2 * pp + 1]};
+      want = u64x2{L.pw[2 * pp], L.pw[2 * pp + 1]};
+      wave_sync_lds();
+      const u64x2 miss = want & ~acc;
+      live = (miss.x | miss.y) != 0ull;   // (the per-piece skip, inside the packed layout)
+    }
+    const int slot = lane >> sh, rpi = 64 >> sh;
+    const int nq = sh == 5 ? RIF : GP_PACK_RIF;
+    u64x2 r[RIF];
+    u64 pieces = 0;   // (an octet of lanes is a line in every layout)
+#pragma unroll
+    for (int q = 0; q < RIF; ++q) {
+      const int k = k0 + slot + q * rpi;
+      const bool on = q < nq && k < cnt && live;
+      r[q] = u64x2{0, 0};
+      if (on) r[q] = load_piece<64>(a.rows, idx[k], pp);
+      pieces += line_pieces<64>(__ballot(on));
+    }
+#pragma unroll
+    for (int q = 0; q < RIF; ++q) acc |= r[q];
+    st.add(S_GATHERED, (u64)min(nq * rpi, cnt - k0));
+    st.add(S_ROW_BYTES, pieces * 16ull);
+    k0 += nq * rpi;
+    // OR over the row slots, in place (lanes 2^sh apart hold the same piece)
+#pragma unroll
+    for (int s = 8; s < 64; s <<= 1) {
+      if (s >> sh) {
+        acc.x |= __shfl_xor(acc.x, s);
+        acc.y |= __shfl_xor(acc.y, s);
+      }
+    }
+    const u64x2 miss = want & ~acc;
+    live = (miss.x | miss.y) != 0ull;
+    const uint32_t b = (uint32_t)__ballot(live);   // (every slot alike: slot 0's octets name the lines)
+    if (sh == 5) lm = lines_of(b);
+    else lm = ((b & 0xFFu) ? 1u << lp_nth_line(lm, 0) : 0u) | ((sh == 4 && (b & 0xFF00u)) ? 1u << lp_nth_line(lm, 1) : 0u);
+    done = lm == 0u;
+  }
+  if (sh != 5) {   // back to the row layout
+    if ((lane >> sh) == 0) {
+      L.pa[2 * pp] = acc.x;
+      L.pa[2 * pp + 1] = acc.y;
+    }
+    wave_sync_lds();
+    acc = u64x2{L.pa[2 * lw], L.pa[2 * lw + 1]};
+    want = u64x2{L.pw[2 * lw], L.pw[2 * lw + 1]};
+    wave_sync_lds();
+  }
+  return done;
+}
+
 // SCAN_LINES rounds (W = 64, filtered, no early exit): staged entries carry the
 // sender's line mask in their low 4 bits ((u << 4) | lines, n <= 2^27), and
 // each lane loads its 16-B piece of a row only when its 128-B line is named.
@@ -657,8 +780,9 @@ __device__ __forceinline__ u64x2 early_exit_target(const ExpandArgs& a, int v, L
 // out elsewhere, so the other variants keep their registers
 template <int W, int MODE, bool DP, class LDS>
 __device__ __forceinline__ void gather_scan(const ExpandArgs& a, int64_t b, int64_t e, LDS& L, int lane,
-                                            int g, int lw, u64x2& acc, WaveStats& st, bool ee, u64x2 want,
+                                            int g, int lw, u64x2& acc, WaveStats& st, bool ee, u64x2& want,
                                             int32_t col0 = INT32_MIN) {
+  // (want: changed by no variant; the packed gather parks it and hands it back)
   // col0: this lane's column id of the first pass, when the caller loaded it
   // early (beside the early-exit target's loads; INT32_MIN: not loaded)
   for (int64_t j0 = b; j0 < e; j0 += 64) {
@@ -728,7 +852,13 @@ __device__ __forceinline__ void gather_scan(const ExpandArgs& a, int64_t b, int6
       cnt = stage_pass(L, ent);
       if (cnt == 0) continue;
     }
-    const bool stop = gather_rows<W>(a, L.idx, cnt, g, lw, acc, st, ee, want);
+    bool stop;
+    if constexpr (W == 64 && (MODE & SCAN_PACK) != 0) {   // (the variant runs early-exit rounds only)
+      stop = ee ? gather_rows_pack(a, L, L.idx, cnt, g, lw, acc, st, want)
+                : gather_rows<W>(a, L.idx, cnt, g, lw, acc, st, ee, want);
+    } else {
+      stop = gather_rows<W>(a, L.idx, cnt, g, lw, acc, st, ee, want);
+    }
     wave_sync_lds();
     if (stop) break;
   }

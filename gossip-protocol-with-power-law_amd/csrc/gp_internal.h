@@ -300,6 +300,8 @@ struct Ctx {
   int32_t ld_env = -1;              // GP_LINE_DONE in the environment at gp_create: 0 off, 1 on, -1 by size
   int32_t ld_min_deg = 0;           // GP_LINE_DONE_MIN_DEG there, else the compile-time default
   bool line_done_now = false;       // this round's pull seeds its targets from d_ldone
+  int32_t lp_env = -1;              // GP_LINE_PACK in the environment at gp_create: 0 off, 1 on, -1 by size
+  bool line_pack_now = false;       // this round's pull runs the packed gather (SCAN_PACK)
 
   // rccl
   ncclComm_t comm = nullptr;

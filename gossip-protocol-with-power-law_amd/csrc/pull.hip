@@ -29,7 +29,11 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
   constexpr bool DPROBE = (MODE & SCAN_DPROBE) != 0;
   constexpr bool LIST = (MODE & SCAN_LIST) != 0;
   constexpr bool QUADS = (MODE & SCAN_QUADS) != 0;
-  constexpr int SCAN = MODE & ~(SCAN_ALIVE | SCAN_DPROBE | SCAN_LIST | SCAN_QUADS);
+  // the serial loop's row gather packs the live lines (gather_rows_pack): a
+  // variant of its own, launched only in gated rounds (launch_expand's choice)
+  constexpr bool PACK = (MODE & SCAN_PACK) != 0;
+  static_assert(!PACK || (W == 64 && !ALIVE && !DPROBE && !LIST && !QUADS), "the packed gather: the plain W = 64 pull");
+  constexpr int SCAN = MODE & ~(SCAN_ALIVE | SCAN_DPROBE | SCAN_LIST | SCAN_QUADS | SCAN_PACK);
   // the variants that can append this round's survivors to the next list
   // (profiles/r06_ab_lists_c5.txt)
   constexpr bool EMIT = W == 64 && (SCAN == SCAN_FILTERED || SCAN == SCAN_UNFILTERED);
@@ -371,7 +375,7 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
           }
         }
       } else {
-        gather_scan<W, SCAN, DPROBE>(a, vb, ve, L, lane, g, lw, acc, st, ee, want, col0);
+        gather_scan<W, SCAN | (PACK ? SCAN_PACK : 0), DPROBE>(a, vb, ve, L, lane, g, lw, acc, st, ee, want, col0);
       }
       reduce_slots<W>(acc);
       if constexpr (ALIVE) {   // the round's gather covered every alive message v lacked: sated
@@ -432,6 +436,7 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
 #define EXPAND_VARIANTS(V)                                                                         \
   V(SCAN_FILTERED, 1) V(SCAN_MASKED, 1) V(SCAN_UNFILTERED, 1) V(SCAN_PRE, 1)                       \
   V(SCAN_UNFILTERED | SCAN_QUADS, 8)                                                               \
+  V(SCAN_UNFILTERED | SCAN_PACK, 64)                                                               \
   V(SCAN_UNFILTERED | SCAN_ALIVE, 32) V(SCAN_PRE | SCAN_ALIVE, 32) V(SCAN_FILTERED | SCAN_ALIVE, 32) \
   V(SCAN_UNFILTERED | SCAN_ALIVE | SCAN_QUADS, 64)                                                 \
   V(SCAN_UNFILTERED | SCAN_DPROBE, 64) V(SCAN_FILTERED | SCAN_DPROBE, 64)                          \
@@ -519,6 +524,12 @@ static PullChoice choose_pull(const Ctx* c, const ExpandArgs& a, int W) {
     else if (a.dprobe && built(scan | SCAN_DPROBE)) p.mode = scan | SCAN_DPROBE;   // (done-probe rounds, launch_expand)
     else if ((a.alias || a.near_done) && built(scan | SCAN_QUADS)) p.mode = scan | SCAN_QUADS;
     else p.mode = scan;
+    // the packed gather: the plain pull, its serial loop's
+    // lanes dealt out over the live lines.  (Not the quads variant, whose
+    // receivers of in-degree <= 32 go through gather_pairs: with the serial
+    // loop alone packed it took 76 VGPRs against 72 and C4 round 4 ran 6.42 ->
+    // 7.14 ms, profiles/r11_ab_line_pack.txt)
+    if (c->line_pack_now && p.mode == scan && built(scan | SCAN_PACK)) p.mode |= SCAN_PACK;
   } else if (a.nloc > 0) {
     p.kernel = PULL_RECEIVER;
     const int pre = c->prefilter_now ? SCAN_PRE : SCAN_FILTERED;

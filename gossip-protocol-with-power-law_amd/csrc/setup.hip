@@ -544,6 +544,9 @@ int gp_create(int device, gp_ctx** out) {
     const long k = strtol(e, nullptr, 10);
     if (k >= 1 && k <= INT32_MAX) c->ld_min_deg = (int32_t)k;
   }
+  // the packed gather of the early-exit pulls: GP_LINE_PACK=0 /
+  // 1 forces it off / on in every eligible round whatever the overlay's size
+  if (const char* e = getenv("GP_LINE_PACK")) c->lp_env = e[0] == '1' ? 1 : e[0] == '0' ? 0 : -1;
   c->curve_grid = curve_env_grid();   // (a test lever, as GP_FINALIZE_ROWS: few blocks fill k_curve's planes)
   c->curve_yard = curve_env_yardstick();
   hipDeviceProp_t prop;
