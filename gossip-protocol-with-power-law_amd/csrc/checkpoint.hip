@@ -236,8 +236,6 @@ int gp_checkpoint_load(gp_ctx* c, const void* host, int64_t bytes) {
   c->prev_new_bits = h.prev_new_bits;
   c->prev_receivers = h.prev_receivers;
   c->held_bits = h.held_bits;
-  c->cml_written_prev = false;   // compact lists are rebuilt by the next sparse round
-  c->cml_read_now = c->cml_write_now = false;
   c->last_reports = h.last_reports;
   // the spread curve is not in the blob (as the job record): a
   // run restored at round 0 has counted nothing yet and keeps the cleared one

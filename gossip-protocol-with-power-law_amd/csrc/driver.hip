@@ -9,8 +9,9 @@
 //   I_r  injection of messages generated in round r     (Peer.py:395-400; k_inject)
 //   E_r  expansion: next[v] = OR_{u in In(v)} frontier[u] & ~seen[v]; seen |= next
 //        (forward-once with the Message-List slots; the send loop is
-//        Peer.py:402-404, the receive side Peer.py:175-216).  launch_expand
-//        picks the direction and scan mode; pull.hip / push.hip / hub.hip run it
+//        Peer.py:402-404, the receive side Peer.py:175-216).  round_plan.h
+//        picks the direction and scan mode (launch_expand gathers its facts
+//        and enqueues the plan); pull.hip / push.hip / hub.hip run it
 //   X_r  (multi-GPU) counters' all-reduce, or the vertex partition's boundary
 //        exchange over RCCL (partition.hip)
 //
@@ -320,7 +321,9 @@ __global__ __launch_bounds__(BLOCK) void k_bitsum(BitsumArgs a) {
   }
 }
 
+// the pull's argument block for this round's plan
 static void fill_expand(Ctx* c, ExpandArgs& a) {
+  const RoundPlan& p = c->plan;
   a.alive = alive_now(c) ? c->d_alive + (size_t)c->cur * c->words : nullptr;
   a.alive_next = alive_on(c) ? c->d_alive + (size_t)(c->cur ^ 1) * c->words : nullptr;
   a.row_ptr = c->d_row_ptr;
@@ -333,18 +336,18 @@ static void fill_expand(Ctx* c, ExpandArgs& a) {
   a.ws = c->d_ws;
   a.fpop = c->d_fpop[c->cur];
   a.abits = c->d_abits;
-  a.sbits = c->sum_now ? c->d_sbits : nullptr;
-  a.dbits = c->dnb_now ? c->d_dbits : nullptr;
+  a.sbits = p.sum ? c->d_sbits : nullptr;
+  a.dbits = p.dnb ? c->d_dbits : nullptr;
   a.amask = c->d_amask;
-  a.prehi = c->split_now ? c->d_prehi : nullptr;
+  a.prehi = p.split ? c->d_prehi : nullptr;
   a.split_push = 0;
-  a.acc_row = c->split_now ? c->acc_row : 0;
-  a.lm = c->lines_now ? (c->lm_written_prev ? c->d_lmw[c->cur] : c->d_lm) : nullptr;
-  a.lm_next = c->lm_write_now ? c->d_lmw[c->cur ^ 1] : nullptr;
-  a.cmk = c->cml_read_now ? c->d_cmk[c->cur] : nullptr;
-  a.cml = c->cml_read_now ? c->d_cml[c->cur] : nullptr;
-  a.cmk_next = c->cml_write_now ? c->d_cmk[c->cur ^ 1] : nullptr;
-  a.cml_next = c->cml_write_now ? c->d_cml[c->cur ^ 1] : nullptr;
+  a.acc_row = p.split ? c->acc_row : 0;
+  a.lm = p.lines ? (c->carry.lm_written ? c->d_lmw[c->cur] : c->d_lm) : nullptr;
+  a.lm_next = p.lm_write ? c->d_lmw[c->cur ^ 1] : nullptr;
+  a.cmk = p.cml_read ? c->d_cmk[c->cur] : nullptr;
+  a.cml = p.cml_read ? c->d_cml[c->cur] : nullptr;
+  a.cmk_next = p.cml_write ? c->d_cmk[c->cur ^ 1] : nullptr;
+  a.cml_next = p.cml_write ? c->d_cml[c->cur ^ 1] : nullptr;
   a.frx = c->d_frx[0] ? c->d_frx[c->cur] : nullptr;
   a.frx_next = c->d_frx[0] ? c->d_frx[c->cur ^ 1] : nullptr;
   a.frx_rows = c->frx_rows;
@@ -352,12 +355,16 @@ static void fill_expand(Ctx* c, ExpandArgs& a) {
   a.gcol = c->d_gcol;
   a.midx = c->d_midx;
   a.cmask = c->d_cmask;
-  a.early_exit = c->early_exit_now ? 1 : 0;
-  a.dprobe = c->dprobe_now ? 1 : 0;
-  a.alias = c->alias_now ? 1 : 0;
-  a.ulist = c->ulist_read_now ? c->d_ulist[c->ul_cur] : nullptr;
-  a.ulist_n = c->ulist_read_now ? c->ulist_n : 0;
-  a.ulist_next = c->ulist_emit_now ? c->d_ulist[c->ul_cur ^ 1] : nullptr;
+  a.unfiltered = p.unfiltered ? 1 : 0;
+  a.near_done = p.near_done ? 1 : 0;
+  a.sate = p.sate ? 1 : 0;
+  a.ldone = p.line_done ? c->d_ldone : nullptr;
+  a.early_exit = p.early_exit ? 1 : 0;
+  a.dprobe = p.dprobe ? 1 : 0;
+  a.alias = p.alias ? 1 : 0;
+  a.ulist = p.ulist_read ? c->d_ulist[c->carry.ul_cur] : nullptr;
+  a.ulist_n = p.ulist_read ? c->carry.ulist_n : 0;
+  a.ulist_next = p.ulist_emit ? c->d_ulist[c->carry.ul_cur ^ 1] : nullptr;
   a.fpop_next = c->d_fpop[c->cur ^ 1];
   a.seenpop = c->d_seenpop;
   a.first = c->cfg.track_first ? c->d_first : nullptr;
@@ -390,279 +397,87 @@ static void fill_expand(Ctx* c, ExpandArgs& a) {
   a.stats = c->d_stats;
 }
 
+// what plan_round reads, from the context
+static RoundFacts round_facts(const Ctx* c) {
+  RoundFacts f;
+  f.n = c->n;
+  f.n_alloc = c->n_alloc;
+  f.nloc = c->nloc();
+  f.nnz = c->nnz;
+  f.m = c->m;
+  f.words = c->words;
+  f.round = c->round;
+  f.cfg = c->cfg;
+  f.prev_new_bits = c->prev_new_bits;
+  f.prev_receivers = c->prev_receivers;
+  f.prev_next_arcs = c->prev_next_arcs;
+  f.held_bits = c->held_bits;
+  f.inj_arcs = (size_t)c->round < c->inj_arcs.size() ? (u64)c->inj_arcs[(size_t)c->round] : 0ull;
+  f.inj_groups = c->inj_groups_at(c->round);
+  f.last_inject_round = c->last_inject_round;
+  f.local = c->local;
+  f.liveness_active = c->liveness_active;
+  f.alive_on = alive_on(c);
+  f.alive_now = alive_now(c);
+  f.have_cml = c->d_cml[0] != nullptr;
+  f.have_lm = c->d_lm != nullptr;
+  f.have_lmw = c->d_lmw[0] != nullptr;
+  f.have_ldone = c->d_ldone != nullptr;
+  f.have_ld_cand = c->n_ld_cand > 0;
+  // accumulator rows as rows of this round's slot buffer: same allocation, same stride
+  const int64_t row = c->words > 0 ? (int64_t)(c->d_acc - c->d_slot[c->cur]) / c->words : 0;   // (d_rows: S[0] | S[1] | acc)
+  f.acc_row = row > 0 && row + c->nloc() <= (int64_t)INT32_MAX ? row : 0;
+  f.ld_env = c->ld_env;
+  f.lp_env = c->lp_env;
+  f.can_park = !c->carry.park_failed;
+  f.carry = c->carry;
+  return f;
+}
 
-#ifndef GP_EE_DIV
-#define GP_EE_DIV 16.0
-#endif
-// rows of <= 8 words (the 512-message shards of an 8-GPU job) take the
-// edge-parallel kernel, whose early-exit variant costs one 2-arc prefix pass
-// when receivers cannot complete: it pays from m/64 new bits per vertex.  The
-// shards of the slower messages cross m/16 a round late, and their dense
-// round then gathered every active row (profiles/r05_ee_shards.txt: ranks 5-6
-// of the N = 8 job 11.3-11.4 -> 8.7-9.0 ms; W = 16 and 64 keep m/16, the
-// 1024-message shard's round 3 lost 0.7 ms at m/64)
-#ifndef GP_EE_DIV_NARROW
-#define GP_EE_DIV_NARROW 64.0
-#endif
+// E_r: gather the facts, plan the round (round_plan.h), enqueue what the plan says
 static int launch_expand(Ctx* c) {
+  RoundFacts f = round_facts(c);
+  RoundPlan p = plan_round(f);
+  // the buffers a plan may rely on are allocated at first use; without one
+  // the round is planned again (at most once for each)
+  if (p.need_park_slot && !c->d_slot[2] && dalloc(&c->d_slot[2], (size_t)c->n_alloc * c->words) != 0) {
+    (void)hipGetLastError();
+    c->carry.park_failed = f.carry.park_failed = true;   // (out of memory: stay filtered)
+    f.can_park = false;
+    p = plan_round(f);
+  }
+  if (p.need_ulist && !c->d_ulist[0] &&
+      (dalloc(&c->d_ulist[0], (size_t)c->n_alloc) != 0 || dalloc(&c->d_ulist[1], (size_t)c->n_alloc) != 0)) {
+    dfree(&c->d_ulist[0]);   // (out of memory: no lists)
+    dfree(&c->d_ulist[1]);
+    (void)hipGetLastError();
+    f.can_list = false;
+    p = plan_round(f);
+  }
+  c->plan = p;
+  c->acc_row = p.split ? (int32_t)f.acc_row : 0;
   if (alive_on(c))   // F_{r+1} is built by this round's receivers
     GP_HIP(hipMemsetAsync(c->d_alive + (size_t)(c->cur ^ 1) * c->words, 0, (size_t)c->words * 8, c->stream));
-  // direction: push when the senders' arcs are a small share of all arcs
-  const int r = c->round;
-  // early exit pays once frontier rows are dense: >= m/16 new bits per vertex last round
-  // or once most messages are held: receivers then miss a few words at most, and
-  // the word skip loads only those (under churn the component targets may be
-  // out of reach -- a message cut off by crashes -- so the done-skip alone
-  // leaves nearly every receiver scanning whole rows)
-  const double ee_div = c->words <= 8 ? GP_EE_DIV_NARROW : GP_EE_DIV;
-  c->early_exit_now = c->cfg.early_exit != 0 &&
-                      ((double)c->prev_new_bits * ee_div >= (double)c->n * (double)c->m ||
-                       (double)c->held_bits * 2.0 >= (double)c->n * (double)c->m);
-  const u64 inj = (size_t)r < c->inj_arcs.size() ? (u64)c->inj_arcs[(size_t)r] : 0ull;
-  const double est = (double)((r == 0 ? 0ull : c->prev_next_arcs) + inj);
-  // narrow rows push at a lower ratio: the pull's per-arc scan does not
-  // shrink with W, the push's row words do (k_apply_lanes, k_mkneed)
-#ifndef GP_NARROW_PUSH_SCALE
-#define GP_NARROW_PUSH_SCALE 0.25
-#endif
-  // (early rounds only: late rounds' pulls skip the done receivers, which the
-  // estimate does not see -- the 512-message shard's round 6 pulls in 0.27 ms
-  // and pushes in 0.72)
-  const bool early = (double)c->held_bits * 2.0 < (double)c->n * (double)c->m;
-#ifndef GP_NARROW_PUSH_MAXW
-#define GP_NARROW_PUSH_MAXW 16
-#endif
-  const double ratio = c->cfg.push_ratio * (c->words <= GP_NARROW_PUSH_MAXW && early ? GP_NARROW_PUSH_SCALE : 1.0);
-  c->mode_push = c->cfg.push_ratio > 0.0 && est * ratio <= (double)c->nnz;
-  // last round's receivers + this round's injected origins send this round
-  const double senders = (double)c->prev_receivers + (double)c->inj_groups_at(r);
-  // narrow rows: a round that pushes only because of the narrow scale pulls
-  // as a degree-split round instead (its prefix probes are a fraction of the
-  // arcs, its push half only the low-degree senders' arcs) -- but only when
-  // the pull would be one: the conditions of unfiltered_now, arc_mask_now,
-  // prefilter_now and split_now below, for a pull (records: W = 64 only;
-  // 512-message shard 14.62 -> 14.16 ms, profiles/r04_ab_shards.txt)
-  const bool pull_unfiltered = c->cfg.unfiltered_pct > 0 &&
-                               senders * 100.0 >= (double)c->cfg.unfiltered_pct * (double)c->n;
-  const bool pull_masked = !pull_unfiltered && c->cfg.arc_mask_permille > 0 &&
-                           senders * 1000.0 >= (double)c->cfg.arc_mask_permille * (double)c->n;
-  const bool pull_splits = c->cfg.split_deg > 0 && !c->early_exit_now && !c->local && c->nloc() == c->n_alloc &&
-                           c->words < 64 && !pull_unfiltered && !pull_masked && c->cfg.prefilter_pct > 0 &&
-                           senders * 100.0 < (double)c->cfg.prefilter_pct * (double)c->n &&
-                           senders * 1000.0 < (double)c->cfg.split_max_permille * (double)c->n;
-  const bool narrow_split = c->mode_push && pull_splits && est * c->cfg.push_ratio > (double)c->nnz;
-  if (narrow_split) c->mode_push = false;
-  c->push_est = est;
-  if (c->mode_push && c->nloc() > 0)
-    GP_HIP(hipMemsetAsync(c->d_fpop[c->cur ^ 1], 0, (size_t)c->nloc() * 4, c->stream));
-  // unfiltered pull when (nearly) every vertex is a sender: last round's
-  // receivers + this round's injected origins >= unfiltered_pct % of n.  With
-  // liveness a crashed vertex's Message-List may hold bits it never sent, so
-  // the down vertices' rows are parked first (k_park; one vertex set per
-  // context, hence not in a vertex partition, whose ghosts' rows are frontiers)
-  c->unfiltered_now = !c->mode_push && c->cfg.unfiltered_pct > 0 &&
-                      senders * 100.0 >= (double)c->cfg.unfiltered_pct * (double)c->n;
-  if (c->unfiltered_now && c->liveness_active) {
-    if (c->local || c->park_failed) {
-      c->unfiltered_now = false;
-    } else if (!c->d_slot[2]) {
-      if (dalloc(&c->d_slot[2], (size_t)c->n_alloc * c->words) != 0) {
-        c->park_failed = true;   // (out of memory: stay filtered)
-        c->unfiltered_now = false;
-        (void)hipGetLastError();
-      }
-    }
-  }
-  // done in-neighbours: without liveness a receiver with an
-  // in-neighbour that held its whole component at the end of the last round
-  // receives exactly cmask & ~seen.  Pull rounds of the per-receiver kernel
-  // once most messages are held (before that hardly any vertex is done, and
-  // the probes only cost); the done bitmap comes with the activity bitmap (one
-  // context: seenpop and done_at share the vertex index)
-  // Narrow rows (W = 8 / 16: the message shards of 4- and 8-GPU jobs) take the
-  // per-receiver kernel instead of the flat one in the thin late rounds (under
-  // 1/NARROW_ND_DIV of the n x m bits still missing): its receivers go
-  // eight / sixteen per wave step (dnb_groups, gather_groups), while the flat
-  // kernel keeps the dense rounds, the last of which leaves a shard ~1 % short
-  // (profiles/r06_ab_narrow_nd.txt; a threshold of n*m/4 or n*m/2 was no
-  // better, n*m/2 slower: LEDGER.md "Receiver groups for the message shards")
-  constexpr double NARROW_ND_DIV = 16;
-  const double nm = (double)c->n * (double)c->m;
-  c->narrow_pr_now = (c->words == 8 || c->words == 16) && c->words <= c->cfg.flat_max_words &&
-                     c->early_exit_now && !c->mode_push && !c->liveness_active && !c->local &&
-                     c->nloc() == c->n_alloc && (nm - (double)c->held_bits) * NARROW_ND_DIV < nm;
-  c->dnb_now = c->early_exit_now && !c->mode_push && !c->liveness_active && !c->local &&
-               c->nloc() == c->n_alloc && (c->words > c->cfg.flat_max_words || c->narrow_pr_now) &&
-               (double)c->held_bits * 2.0 >= (double)c->n * (double)c->m;
-  // With liveness the done bitmap is the sated marks (up and sated: holds every
-  // alive message of its component; k_mkbits): a receiver with such an
-  // in-neighbour receives exactly cmask & F_r & ~seen, since every bit of it
-  // lies in that neighbour's frontier (it sent everything older while both were
-  // up, and crashes are final).  From the round after the first marking round.
-  if (!c->dnb_now && c->liveness_active && alive_now(c) && c->early_exit_now && !c->mode_push &&
-      !c->local && c->nloc() == c->n_alloc && c->words > c->cfg.flat_max_words && c->sate_since >= 0 &&
-      c->round > c->sate_since)
-    c->dnb_now = true;
-  // aliased Message-Lists (W = 64, no liveness, one context,
-  // no compact records): in done-neighbour rounds receivers that complete
-  // commit SLOT_CMASK instead of a 512-B row.  Once a run holds aliases every
-  // pull probes the done bitmap for each arc it scans (a receiver with any
-  // done in-neighbour takes its target, so no aliased row slot is gathered);
-  // held bits only grow, so early exit and the done bitmap stay on.  The
-  // first aliasing round reads rows written before any alias and needs no
-  // probe (C4 round 4: 74.6 M arcs whose probe would sit in each pass's
-  // dependent chain).  A push round first writes its aliased senders' rows
-  // (k_unalias; profiles/r06_ab_alias.txt)
-  const bool alias_ok = c->words == 64 && !c->liveness_active && !c->local && c->nloc() == c->n_alloc &&
-                        c->cfg.compact_rows == 0 && c->words > c->cfg.flat_max_words;
-  c->alias_now = c->dnb_now && alias_ok;
-  c->dprobe_now = c->alias_now && c->alias_active;
-  // receiver lists (W = 64 early-exit pulls, one context):
-  // once most messages are held, each pull appends the receivers that stay
-  // neither done nor sated; a pull whose list is under a third of the
-  // vertices launches waves for those alone, k_mkbits does every sender's
-  // accounting and the receivers' fpop_next starts zeroed (C5 round 6: 1.26 M
-  // receivers of 64 M vertices; profiles/r06_ab_lists_c5.txt)
-  const bool list_ok = !c->mode_push && !c->local && c->nloc() == c->n_alloc && c->words == 64 &&
-                       c->words > c->cfg.flat_max_words && c->cfg.compact_rows == 0 && c->early_exit_now;
-#ifndef GP_ULIST_DIV
-#define GP_ULIST_DIV 3
-#endif
-  c->ulist_read_now = list_ok && c->ulist_valid && c->ulist_n * GP_ULIST_DIV < c->n_alloc;
-  if (c->ulist_read_now)
+  // a push's receivers and a list round's non-receivers start from fpop_next = 0
+  if ((p.mode_push && c->nloc() > 0) || p.ulist_read)
     GP_HIP(hipMemsetAsync(c->d_fpop[c->cur ^ 1], 0, (size_t)c->nloc() * 4, c->stream));
   hipLaunchKernelGGL(k_mkbits, dim3(std::max(1, std::min(grid_for(c->n_alloc, BLOCK), c->cu_count * 8 * GS))),
                      dim3(BLOCK), 0, c->stream, c->d_fpop[c->cur], c->d_abits, c->n_alloc,
-                     c->d_seenpop, c->d_done_at, c->dnb_now ? c->d_dbits : nullptr,
-                     c->dnb_now && c->liveness_active ? (const uint8_t*)c->d_state : nullptr,
-                     c->ulist_read_now ? (const int32_t*)c->d_deg_live : nullptr, c->d_stats + 64);
-  if (c->alias_active) {   // (after k_mkbits: a push round's senders are the activity bitmap's bits)
-    if (c->mode_push) GP_TRY(unalias(c, true));
-    else if (!c->dprobe_now) GP_TRY(unalias(c, false));   // (a pull that could gather a done sender's row)
+                     c->d_seenpop, c->d_done_at, p.dnb ? c->d_dbits : nullptr,
+                     p.dnb && c->liveness_active ? (const uint8_t*)c->d_state : nullptr,
+                     p.ulist_read ? (const int32_t*)c->d_deg_live : nullptr, c->d_stats + 64);
+  if (c->carry.alias_active) {   // (after k_mkbits: a push round's senders are the activity bitmap's bits)
+    if (p.mode_push) GP_TRY(unalias(c, true));
+    else if (!p.dprobe) GP_TRY(unalias(c, false));   // (a pull that could gather a done sender's row)
   }
-  // filtered pull: probe every arc inside the scan, or build the per-arc mask
-  // first (pays once the probes are many: senders >= arc_mask_permille of n)
-  c->arc_mask_now = !c->mode_push && !c->unfiltered_now && c->cfg.arc_mask_permille > 0 &&
-                    senders * 1000.0 >= (double)c->cfg.arc_mask_permille * (double)c->n;
-  // summary probes: filtered rounds of overlays whose activity bitmap outgrows
-  // an XCD's L2, while few enough vertices send that most summary bits are 0
-  c->sum_now = false;
-  if (!c->mode_push && !c->unfiltered_now && !c->arc_mask_now && c->cfg.summary_min_n > 0 &&
-      c->n_alloc >= c->cfg.summary_min_n &&
-      senders * SUMMARY_RATIO <= (double)c->n) {
+  if (p.sum) {
     const int64_t nwords = (c->n_alloc + 63) / 64;
     hipLaunchKernelGGL(k_mksum, dim3(grid_for((nwords + 63) / 64, WAVES)), dim3(BLOCK), 0, c->stream,
                        c->d_abits, c->d_sbits, nwords);
-    c->sum_now = true;
   }
-  // Message-List records (W = 64): written while the rows are sparse (last
-  // round's receivers got <= CML_AVG_BITS new bits on average), read by a
-  // filtered pull without early exit whose senders all wrote theirs (or their
-  // dense bit) in the previous round.  Senders are exactly the vertices with
-  // fpop != 0 under liveness too (a crash zeroes fpop), and a sender's record
-  // mirrors its row, so records and full rows give the same OR.
-  {
-    constexpr double CML_AVG_BITS = 16.0;
-    const bool ok = c->d_cml[0] != nullptr && c->words == 64 && !c->mode_push;
-    const bool sparse = (double)c->prev_new_bits <= CML_AVG_BITS * (double)std::max<u64>(c->prev_receivers, 1);
-    c->cml_read_now = ok && c->cml_written_prev && !c->unfiltered_now && !c->arc_mask_now && !c->early_exit_now;
-    c->cml_write_now = ok && sparse && !c->unfiltered_now && !c->arc_mask_now;   // the kernels that write them
-  }
-  // line masks (W = 64): a filtered pull without early exit reads its
-  // senders' rows while they are still sparse; their zero 128-B lines are
-  // skipped.  The launch narrows this to the plain
-  // per-receiver kernel (k_expand<64, SCAN_FILTERED | SCAN_LINES>)
-  c->lines_now = c->words == 64 && c->d_lm != nullptr && !c->mode_push && !c->unfiltered_now &&
-                 !c->arc_mask_now && !c->early_exit_now && c->n_alloc <= (int64_t(1) << 27);   // (u << 4) | lines
-  // this round's 64-word pull commits write the next round's masks: one
-  // context (ghosts' rows come from the exchange), per-receiver kernel, no
-  // records; under liveness k_churn zeroes a crashing sender's nibble with
-  // its fpop (round 4 of the build; k_mklm ran there until then)
-  // (only sparse rounds: a line-mask round follows a round with few new bits,
-  // and early-exit rounds would pay the commits' extra stores for nothing --
-  // C4 rounds 3-4 +0.3 ms when every pull wrote them)
-  c->lm_write_now = c->words == 64 && c->d_lmw[0] != nullptr && !c->mode_push &&
-                    !c->early_exit_now && !c->local && !c->cml_read_now && !c->cml_write_now;
-  // sparse filtered pull: the lane phase probes the in-lists of low-degree receivers
-  c->prefilter_now = !c->mode_push && !c->unfiltered_now && !c->arc_mask_now && c->cfg.prefilter_pct > 0 &&
-                     senders * 100.0 < (double)c->cfg.prefilter_pct * (double)c->n;
-  // degree-split: a prefiltered per-receiver pull without
-  // early exit (C4 / C5 round 1), one context, no compact Message-Lists:
-  // senders of in-degree < split_deg push (few arcs: they are the
-  // low-degree minority of a degree-biased sender set), receivers probe only
-  // the gather-order prefix of bigger senders
-  // Only while the senders are a sliver of the vertices (C4 / C5 round 1:
-  // 0.1-0.4 %): the 512-message shards' round 2, prefiltered with 7-13 % of
-  // the vertices sending, pushed 30-67 M low-degree arcs in 3.3-5.9 ms
-  // against a 1.8-1.9 ms pull half (profiles/r04_split_cap.txt)
-  c->split_now = c->cfg.split_deg > 0 && c->prefilter_now && !c->early_exit_now && !c->local &&
-                 c->nloc() == c->n_alloc && !c->cml_read_now && !c->cml_write_now &&
-                 senders * 1000.0 < (double)c->cfg.split_max_permille * (double)c->n;
-  if (c->split_now) {   // accumulator rows as rows of this round's slot buffer: same allocation, same stride
-    const int64_t row = (int64_t)(c->d_acc - c->d_slot[c->cur]) / c->words;   // (d_rows: S[0] | S[1] | acc)
-    c->split_now = row > 0 && row + c->nloc() <= (int64_t)INT32_MAX;
-    c->acc_row = (int32_t)row;
-  }
-  if (c->dprobe_now || c->ulist_read_now) {   // the scan modes of these variants: filtered and unfiltered
-    c->arc_mask_now = c->prefilter_now = c->split_now = false;
-    c->cml_read_now = c->cml_write_now = c->lines_now = c->lm_write_now = false;
-  }
-  // (only once the rounds thin out: last round's new bits under m/4 per
-  // vertex -- C4 round 4's survivors, 7.6 M, would make no list worth reading,
-  // and appending them cost the round 0.07 ms)
-  c->ulist_emit_now = list_ok && (double)c->held_bits * 2.0 >= (double)c->n * (double)c->m &&
-                      (double)c->prev_new_bits * 4.0 < (double)c->n * (double)c->m && !c->arc_mask_now &&
-                      !c->prefilter_now && !c->split_now && !c->cml_read_now && !c->cml_write_now && !c->lines_now;
-  if (c->ulist_emit_now && !c->d_ulist[0]) {
-    if (dalloc(&c->d_ulist[0], (size_t)c->n_alloc) != 0 || dalloc(&c->d_ulist[1], (size_t)c->n_alloc) != 0) {
-      dfree(&c->d_ulist[0]);   // (out of memory: no lists)
-      dfree(&c->d_ulist[1]);
-      c->ulist_emit_now = false;
-      (void)hipGetLastError();
-    }
-  }
-  if (narrow_split && !c->split_now)   // (the conditions above mirror these: a pull was promised a split)
-    return set_error(GP_ESTATE, "internal: narrow-row split round not eligible");
-  if (c->split_now) GP_TRY(build_prehi(c, c->cfg.split_deg));
+  if (p.split) GP_TRY(build_prehi(c, c->cfg.split_deg));
   ExpandArgs a{};
   fill_expand(c, a);
-  a.unfiltered = c->unfiltered_now ? 1 : 0;
-  // (not with liveness: messages cut off by crashes keep the component targets
-  // out of reach, receivers scan to the end and want every row in flight --
-  // C5 rounds 5-6 56.8 -> 64.3 ms with the switch on)
-  a.near_done = c->early_exit_now && !c->liveness_active &&
-                (double)c->held_bits * 2.0 >= (double)c->n * (double)c->m ? 1 : 0;
-  // sated vertices (churn): with no injection left, a receiver that ends the
-  // round holding every alive message of its component never receives again
-  a.sate = alive_now(c) && c->early_exit_now && c->round >= c->last_inject_round ? 1 : 0;
-  if (a.sate && c->sate_since < 0) c->sate_since = c->round;
-  // Complete lines of a top in-neighbour: the unfiltered
-  // early-exit pulls of k_expand<64> that read no receiver list (an aliased
-  // candidate of a done-probe round holds every line: no row is read), under
-  // alias_ok's conditions.  By default only where it paid: once the
-  // Message-Lists outgrow the Infinity Cache (n_alloc x 8W > 256 MiB: below
-  // that the dense rounds are not HBM-bound) and before the done-neighbour
-  // rounds (C4 round 3: 71.1 -> 47.6 GB of row bytes, 16.0 -> 14.5 ms; round
-  // 4's row bytes fell by 21 % too, but the round, which waits on the
-  // per-receiver chain, ran 0.07 ms slower: profiles/r09_ab_line_done.txt).
-  // GP_LINE_DONE=1 turns it on in every eligible round whatever the size,
-  // GP_LINE_DONE=0 off
-  const bool ld_big = (double)c->n_alloc * 8.0 * (double)c->words > 256.0 * 1024.0 * 1024.0;
-  c->line_done_now = alias_ok && c->early_exit_now && c->unfiltered_now && !c->mode_push &&
-                     !c->ulist_read_now && c->d_ldone != nullptr && c->n_ld_cand > 0 &&
-                     (c->ld_env < 0 ? ld_big && !c->dnb_now : c->ld_env == 1);
-  a.ldone = c->line_done_now ? c->d_ldone : nullptr;
-  // The packed gather: the same pulls -- k_expand<64>'s
-  // unfiltered early-exit rounds without liveness, receiver list or done
-  // probe.  By default under the per-line rule's size gate (the live lines
-  // collapse to one under the spread order at W = 64, and nothing was measured
-  // below that size) and before the done-neighbour rounds (the plain variant,
-  // C4 round 3).  GP_LINE_PACK=1 turns it on in every eligible round whatever
-  // the size, GP_LINE_PACK=0 off
-  c->line_pack_now = alias_ok && c->early_exit_now && c->unfiltered_now && !c->mode_push &&
-                     !c->ulist_read_now && !c->dprobe_now &&
-                     (c->lp_env < 0 ? ld_big && !c->dnb_now : c->lp_env == 1);
-  c->lines_ran = c->lines_from_commits = false;
   return launch_round_kernels(c, a);
 }
 
@@ -740,7 +555,7 @@ static int round_launch(Ctx* c) {
     ia.first = c->cfg.track_first ? c->d_first : nullptr;
     ia.digest = c->cfg.track_digest ? c->d_digest : nullptr;
     ia.state = c->d_state;
-    ia.lm = c->lm_written_prev ? c->d_lmw[c->cur] : nullptr;
+    ia.lm = c->carry.lm_written ? c->d_lmw[c->cur] : nullptr;
     ia.partial = partial;
     ia.off = it->second.off;
     ia.groups = it->second.cnt;
@@ -833,13 +648,10 @@ static int round_collect(Ctx* c, gp_round_stats* out) {
     out->atomics = h[S_ATOMICS];
     out->next_arcs = h[S_NEXT_ARCS];
     out->row_bytes = h[S_ROW_BYTES];
-    out->mode = c->mode_push ? 1 : 0;
-    out->scan = c->mode_push ? 0 : (c->unfiltered_now ? 2 : c->arc_mask_now ? 1 : c->prefilter_now ? 3 : 0) |
-                                       (c->cml_read_now ? 4 : 0) | (c->lines_ran ? 8 : 0) |
-                                       (c->lines_from_commits ? 16 : 0) | (c->split_now ? 32 : 0) |
-                                       (c->dprobe_now ? 64 : 0) | (c->ulist_read_now ? 128 : 0);
+    out->mode = c->plan.mode_push ? 1 : 0;
+    out->scan = c->plan.scan();
     out->kernel_ms = 0.0;
-    if (!c->mode_push && c->nloc() > 0) {
+    if (!c->plan.mode_push && c->nloc() > 0) {
       float kms = 0.f;
       (void)hipEventElapsedTime(&kms, c->ev[4], c->ev[5]);
       out->kernel_ms = kms;
@@ -865,15 +677,19 @@ static int round_collect(Ctx* c, gp_round_stats* out) {
   c->prev_new_bits = h[S_NEW_BITS];
   c->prev_receivers = h[S_RECEIVERS];
   c->held_bits += h[S_INJECTED] + h[S_NEW_BITS];
-  c->cml_written_prev = c->cml_write_now;
-  c->lm_written_prev = c->lm_write_now;
-  if (h[S_ALIASED]) c->alias_active = true;
-  c->ulist_valid = c->ulist_emit_now;   // (a round that appends no list ends the last one)
-  if (c->ulist_emit_now) {
-    c->ulist_n = (int64_t)h[S_ULIST];
-    c->ul_cur ^= 1;
+  {   // what this round hands to the next one
+    const RoundPlan& p = c->plan;
+    RoundCarry& k = c->carry;
+    k.cml_written = p.cml_write;
+    k.lm_written = p.lm_write;
+    if (h[S_ALIASED]) k.alias_active = true;
+    k.ulist_valid = p.ulist_emit;   // (a round that appends no list ends the last one)
+    if (p.ulist_emit) {
+      k.ulist_n = (int64_t)h[S_ULIST];
+      k.ul_cur ^= 1;
+    }
+    if (p.sate && k.sate_since < 0) k.sate_since = r;
   }
-  c->ulist_emit_now = c->ulist_read_now = false;
   c->cur ^= 1;
   c->round = r + 1;
   return 0;

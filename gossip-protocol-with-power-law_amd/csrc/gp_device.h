@@ -12,6 +12,7 @@
 
 #include "gp_internal.h"
 #include "line_pack.h"
+#include "round_plan.h"
 
 namespace gp {
 
@@ -252,8 +253,6 @@ constexpr int CML_MAXW = CML_WORDS - 1;   // nonzero words a record holds
 #ifndef GP_DETECT_BLOCKS_PER_CU
 #define GP_DETECT_BLOCKS_PER_CU 16   // 4 -> 16: C5 304.1-304.5 -> 302.2-302.4 ms per run same-box
 #endif
-// summary probes only while at most n / SUMMARY_RATIO vertices send
-constexpr double SUMMARY_RATIO = 256.0;
 #define EXPAND_BOUNDS __launch_bounds__(EBLOCK)
 // rows each lane keeps in flight per gather step (MLP vs VGPRs)
 #ifndef GP_ROWS_IN_FLIGHT
@@ -268,7 +267,7 @@ constexpr double SUMMARY_RATIO = 256.0;
 #define GP_ROWS_IN_FLIGHT_64 3
 #endif
 // W = 8: the per-receiver kernel runs the 8-GPU job's thin late rounds
-// (narrow_pr_now); 2 rows in flight keep it at ~59 VGPRs against ~103 with 4
+// (plan.narrow_pr); 2 rows in flight keep it at ~59 VGPRs against ~103 with 4
 // (N = 8 slowest rank 11.8 -> 11.3 ms, profiles/r06_ab_w8.txt)
 #ifndef GP_ROWS_IN_FLIGHT_NARROW
 #define GP_ROWS_IN_FLIGHT_NARROW 2
@@ -409,33 +408,8 @@ __device__ __forceinline__ void reduce_slots(u64x2& acc) {
   }
 }
 
-// scan modes of a pull round (compile-time): the per-arc activity probe, the
-// per-arc activity mask built by k_arcmask before the round, or no check at all
-// (unfiltered dense rounds)
-enum ScanMode { SCAN_FILTERED = 0, SCAN_MASKED = 1, SCAN_UNFILTERED = 2, SCAN_PRE = 3,
-                SCAN_CML = 4 /* flag: read / write compact Message-Lists (W = 64) */,
-                SCAN_ALIVE = 8 /* flag: early-exit targets narrowed to the alive messages (k_expand);
-                                  a variant of its own: +2-3 VGPRs cost a wave per SIMD */,
-                SCAN_LINES = 32 /* flag (W = 64, filtered): the probe reads the sender's line mask
-                                   (k_mklm) and the gather loads only its nonzero 128-B lines */,
-                SCAN_DPROBE = 64 /* flag (k_expand, W = 64, filtered / unfiltered): every scanned arc
-                                    probes the done bitmap (a.dprobe rounds, aliased Message-Lists);
-                                    a variant of its own: +4 VGPRs cost the unfiltered pull a wave */,
-                SCAN_LIST = 128 /* flag (k_expand, W >= 32, filtered / unfiltered): the waves take
-                                   their receivers from a.ulist, the vertices that could still
-                                   receive (late rounds), not 64 consecutive ids */,
-                SCAN_QUADS = 256 /* flag (k_expand, unfiltered): W = 64: done-neighbour receivers
-                                    four per wave step (dnb_quads) without the done probe, and (no
-                                    liveness) receivers of in-degree <= 32 two per step
-                                    (gather_pairs): the first aliasing round, near-done pulls,
-                                    alive pulls from the half-held round; W = 32 / 16 / 8
-                                    near-done pulls: low in-degree receivers 4 / 8 / 16 per step
-                                    (gather_groups) */,
-                SCAN_PACK = 512 /* flag (k_expand, W = 64, unfiltered early-exit pulls without liveness,
-                                   list or done probe): the serial loop's row gather deals its lanes
-                                   out over the lines the receiver still misses (gather_rows_pack);
-                                   a variant of its own: 1 KB of LDS per wave, and the other
-                                   variants keep their code */ };
+// (the scan modes of a pull round, ScanMode, and the table of the k_expand
+// variants that are built: round_plan.h)
 
 // activity bits of arcs [j0, j0 + n) (n <= 64) from the per-arc mask, bit t =
 // arc j0 + t; j0 wave-uniform, so both words come in through scalar loads

@@ -11,6 +11,7 @@
 
 #include "../../include/gossip_capi.h"
 #include "gp_common.h"
+#include "round_plan.h"
 
 namespace gp {
 
@@ -133,7 +134,7 @@ struct Ctx {
   // parking: an unfiltered pull under liveness reads every in-neighbour's row
   // of slot r & 1, so before it the rows of down vertices move to slot 2
   // (sp = 2) and both read-slot rows are zeroed; slot 2 is allocated lazily
-  bool park_failed = false;         // slot 2 could not be allocated: no unfiltered pull under liveness
+  // (carry.park_failed: it could not be)
   uint8_t* d_sp = nullptr;          // [n_alloc] slot of v's seen row (0xFF: none)
   uint8_t* d_ws = nullptr;          // [n_alloc] bit p: slot p written this run
   u64* d_frx[2] = {nullptr, nullptr};     // exact frontier rows (track_msg_forwards; partitioned; spread curve)
@@ -162,8 +163,11 @@ struct Ctx {
   uint32_t* d_det_live = nullptr;
   uint32_t* d_det_cur = nullptr;
   u64* d_det_base = nullptr;
+  // this round's plan (round_plan.h: direction, scan mode, every switch of
+  // the pull, its kernel) and what the run's rounds hand to the next one
+  RoundPlan plan;
+  RoundCarry carry;
   // [n_alloc/64] frontier_r activity bitmap (fpop != 0): 2 MB at 2^24
-  double push_est = 0.0;            // sender arcs the direction estimate saw this round
   u64* d_nbits = nullptr;           // [n_alloc/64] narrow push rounds: receivable vertices (k_mkneed)
   u64* d_abits = nullptr;
   u64* d_sbits = nullptr;   // summary level of d_abits (summary probes)
@@ -171,41 +175,21 @@ struct Ctx {
   // context): bit v = v held every message of its component at the end of the
   // last round (done in-neighbours)
   u64* d_dbits = nullptr;
-  bool dnb_now = false;             // this round's pull reads d_dbits
-  bool narrow_pr_now = false;       // W = 8 / 16 near-done pull on the per-receiver kernel (launch_expand)
-  int32_t sate_since = -1;          // first round that marked sated vertices (-1: none yet this run)
   // [n_alloc] line masks (W = 64): bit l = 128-B line l of v's
   // row in this round's slot holds a nonzero word; 0 = not a sender.  Built by
   // k_mklm from the very rows the round's filtered pull reads (SCAN_LINES)
   uint8_t* d_lm = nullptr;
-  bool lines_now = false;
   // [2][n_alloc / 2] the same masks written by the commits of a 64-word pull
   // for the next round's senders (nibbles, by round parity like d_fpop): a
   // line-mask round after such a round (no liveness, one context) probes them
   // without k_mklm's pass over the senders' rows
   uint8_t* d_lmw[2] = {nullptr, nullptr};
-  bool lm_write_now = false, lm_written_prev = false;
-  // what this round's pull actually ran (round stats' scan bits 8 / 16): the
-  // line-mask variant, and with masks the previous round's commits wrote
-  bool lines_ran = false, lines_from_commits = false;
-  bool split_now = false;   // degree-split round: low-degree senders push, receivers probe a prefix
-  // aliased Message-Lists: a receiver that completes its
-  // component in a W = 64 early-exit pull writes no row; sp = SLOT_CMASK says
-  // its Message-List is cmask[midx[v]].  dprobe_now: the pull probes the done
-  // bitmap for every arc it scans (a receiver with any done in-neighbour takes
-  // its target and gathers nothing, so an aliased row is never gathered);
-  // alias_now: its complete receivers alias; alias_active: the run holds
-  // aliases (readers of rows outside such pulls materialize them, k_unalias)
-  bool dprobe_now = false, alias_now = false, alias_active = false;
   // receiver lists: late early-exit pulls append the
-  // receivers that are still neither done nor sated to d_ulist[ul_cur ^ 1];
+  // receivers that are still neither done nor sated to d_ulist[carry.ul_cur ^ 1];
   // the next pull, when the list is short, launches waves for those alone
   // (SCAN_LIST) and leaves the senders' accounting to k_mkbits
   int32_t* d_ulist[2] = {nullptr, nullptr};
-  int ul_cur = 0;
-  bool ulist_valid = false, ulist_emit_now = false, ulist_read_now = false;
-  int64_t ulist_n = 0;
-  int32_t acc_row = 0;      // its accumulator rows addressed as rows of the round's slot buffer
+  int32_t acc_row = 0;      // a degree-split round's accumulator rows as rows of its slot buffer
   // [nnz/64 + 2] per-arc activity mask of filtered pull rounds (gcol order): 33.5 MB at C4
   u64* d_amask = nullptr;
   // push (sparse-round) mode
@@ -216,19 +200,12 @@ struct Ctx {
   int32_t* d_big = nullptr;         // [n_alloc] senders above the hub threshold
   std::vector<int64_t> inj_arcs;    // per inject round: sum of origin out-degrees
   u64 prev_next_arcs = 0;           // out-degree sum of the last round's receivers
-  bool mode_push = false;           // direction of the current round
-  bool early_exit_now = false;      // coverage-checked scan this round
   u64 prev_new_bits = 0;            // new bits of the last round (global)
   u64 prev_receivers = 0;           // receivers of the last round (global)
   u64 held_bits = 0;                // messages held so far, summed over vertices (global)
-  bool unfiltered_now = false;      // this round's pull skips the activity check
-  bool arc_mask_now = false;        // this round's filtered pull reads the per-arc mask
-  bool sum_now = false;             // this round's probes read the summary level first
-  bool prefilter_now = false;       // this round's filtered pull probes low-degree in-lists lane-parallel
   // compact Message-Lists: 128-B records per vertex, per slot
   u64* d_cml[2] = {nullptr, nullptr};   // [n_alloc][16] records
   u64* d_cmk[2] = {nullptr, nullptr};   // [n_alloc / 64] dense bitmaps (bit v: no record, read the row)
-  bool cml_read_now = false, cml_write_now = false, cml_written_prev = false;
   int64_t inj_groups_at(int32_t r) const {
     auto it = inject.find(r);
     return it == inject.end() ? 0 : it->second.cnt;
@@ -299,9 +276,7 @@ struct Ctx {
   size_t ldone_bytes = 0;           // its size as allocated
   int32_t ld_env = -1;              // GP_LINE_DONE in the environment at gp_create: 0 off, 1 on, -1 by size
   int32_t ld_min_deg = 0;           // GP_LINE_DONE_MIN_DEG there, else the compile-time default
-  bool line_done_now = false;       // this round's pull seeds its targets from d_ldone
   int32_t lp_env = -1;              // GP_LINE_PACK in the environment at gp_create: 0 off, 1 on, -1 by size
-  bool line_pack_now = false;       // this round's pull runs the packed gather (SCAN_PACK)
 
   // rccl
   ncclComm_t comm = nullptr;

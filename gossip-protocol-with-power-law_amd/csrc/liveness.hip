@@ -528,7 +528,7 @@ int launch_liveness(Ctx* c) {
   la.stats = stats;
   la.partial = partial;
   la.l2g = c->local ? c->d_l2g : nullptr;
-  la.lm = c->lm_written_prev ? c->d_lmw[c->cur] : nullptr;
+  la.lm = c->carry.lm_written ? c->d_lmw[c->cur] : nullptr;
   la.n = c->n_alloc;
   la.vbegin = 0;
   la.vend = c->nloc();

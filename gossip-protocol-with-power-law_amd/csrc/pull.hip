@@ -2,11 +2,12 @@
 // v's in-neighbours u of frontier[u] & ~seen[v] (the send loop of Peer.py:402-404,
 // the receive side of Peer.py:175-216), with forward-once and Message-List
 // dedup.  k_expand (a wave per 64 receivers, one receiver at a time, W >= 32;
-// its receivers several per wave step: pull_groups.h), the choice of the
-// round's pull kernel (k_expand's variants, k_expand_flat of pull_flat.hip,
-// k_expand_rec of pull_rec.hip) and the launch of a whole expansion round
-// with the helper passes of pull_aux.hip.
+// its receivers several per wave step: pull_groups.h) and the launch of a
+// whole expansion round as round_plan.h planned it (k_expand's variants,
+// k_expand_flat of pull_flat.hip, k_expand_rec of pull_rec.hip) with the
+// helper passes of pull_aux.hip.
 #include "pull_groups.h"
+#include "round_plan.h"
 
 namespace gp {
 
@@ -30,7 +31,7 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
   constexpr bool LIST = (MODE & SCAN_LIST) != 0;
   constexpr bool QUADS = (MODE & SCAN_QUADS) != 0;
   // the serial loop's row gather packs the live lines (gather_rows_pack): a
-  // variant of its own, launched only in gated rounds (launch_expand's choice)
+  // variant of its own, launched only in gated rounds (round_plan.h's choice)
   constexpr bool PACK = (MODE & SCAN_PACK) != 0;
   static_assert(!PACK || (W == 64 && !ALIVE && !DPROBE && !LIST && !QUADS), "the packed gather: the plain W = 64 pull");
   constexpr int SCAN = MODE & ~(SCAN_ALIVE | SCAN_DPROBE | SCAN_LIST | SCAN_QUADS | SCAN_PACK);
@@ -429,34 +430,10 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
   flush_stats<EWAVES>(st, a.partial);
 }
 
-// The k_expand<W, MODE> variants that are built: MODE, and the narrowest W it
-// is instantiated for (narrower rows take the flat kernel by default, line
-// masks / records / aliases / receiver lists exist at W = 64 only).  Every
-// width guard of the pull's launch is this table.
-#define EXPAND_VARIANTS(V)                                                                         \
-  V(SCAN_FILTERED, 1) V(SCAN_MASKED, 1) V(SCAN_UNFILTERED, 1) V(SCAN_PRE, 1)                       \
-  V(SCAN_UNFILTERED | SCAN_QUADS, 8)                                                               \
-  V(SCAN_UNFILTERED | SCAN_PACK, 64)                                                               \
-  V(SCAN_UNFILTERED | SCAN_ALIVE, 32) V(SCAN_PRE | SCAN_ALIVE, 32) V(SCAN_FILTERED | SCAN_ALIVE, 32) \
-  V(SCAN_UNFILTERED | SCAN_ALIVE | SCAN_QUADS, 64)                                                 \
-  V(SCAN_UNFILTERED | SCAN_DPROBE, 64) V(SCAN_FILTERED | SCAN_DPROBE, 64)                          \
-  V(SCAN_PRE | SCAN_CML, 64) V(SCAN_FILTERED | SCAN_CML, 64) V(SCAN_FILTERED | SCAN_LINES, 64)     \
-  V(SCAN_UNFILTERED | SCAN_LIST, 64) V(SCAN_FILTERED | SCAN_LIST, 64)                              \
-  V(SCAN_UNFILTERED | SCAN_ALIVE | SCAN_LIST, 64) V(SCAN_FILTERED | SCAN_ALIVE | SCAN_LIST, 64)    \
-  V(SCAN_UNFILTERED | SCAN_DPROBE | SCAN_LIST, 64) V(SCAN_FILTERED | SCAN_DPROBE | SCAN_LIST, 64)
-
-constexpr int expand_min_width(int mode) {
-  switch (mode) {
-#define V(MODE, MINW) case (MODE): return MINW;
-    EXPAND_VARIANTS(V)
-#undef V
-    default: return 1 << 30;   // not built
-  }
-}
-
-// false: no such variant is built for W (choose_pull asks the table first, so
-// this is a mistake in one of the two: the round reports it instead of
-// silently losing its pull)
+// One launch per row of round_plan.h's EXPAND_VARIANTS table.  false: no such
+// variant is built for W (plan_round asks the table first, so this is a
+// mistake in one of the two: the round reports it instead of silently losing
+// its pull)
 template <int W>
 static bool launch_k_expand(Ctx* c, const ExpandArgs& a, int64_t receivers, int mode) {
   const dim3 grid(grid_for(receivers, (int64_t)EWAVES * 64));
@@ -473,82 +450,6 @@ static bool launch_k_expand(Ctx* c, const ExpandArgs& a, int64_t receivers, int 
     default: break;
   }
   return false;
-}
-
-// Which kernel pulls this round, and what its pre- and post-passes need to
-// know.  Launches nothing, changes nothing.
-enum PullKernel { PULL_NONE, PULL_FLAT, PULL_LIST, PULL_RECEIVER, PULL_RECORD };
-struct PullChoice {
-  PullKernel kernel = PULL_NONE;
-  int mode = 0;                   // k_expand's MODE (flat: SCAN_FILTERED / SCAN_UNFILTERED)
-  bool masked = false;            // the per-arc mask is built first (k_arcmask)
-  bool lines = false;             // the senders' line masks are read (SCAN_LINES, hub chunks) ...
-  bool lm_from_commits = false;   // ... as the last round's commits wrote them (else k_mklm builds them)
-};
-
-static PullChoice choose_pull(const Ctx* c, const ExpandArgs& a, int W) {
-  PullChoice p;
-  const auto built = [W](int mode) { return W >= expand_min_width(mode); };
-  const bool unf = a.unfiltered != 0;
-  const int scan = unf ? SCAN_UNFILTERED : SCAN_FILTERED;
-  // the flat kernel (built for W <= 32) up to flat_max_words, 16 by default:
-  // W = 32 rows take the per-receiver kernel in every round, whose receiver
-  // groups beat the flat kernel in the dense near-done rounds too
-  // (profiles/r06_ab_w32_groups.txt), W = 8 / 16 in the thin late rounds
-  const bool flat = W <= 32 && W <= c->cfg.flat_max_words && !c->narrow_pr_now;
-  p.masked = !unf && !flat && c->arc_mask_now;
-  p.lines = built(SCAN_FILTERED | SCAN_LINES) && a.lm != nullptr && !flat && !p.masked && !unf && !a.cmk && !a.cmk_next &&
-            !c->prefilter_now && !(a.alive && a.early_exit);
-  p.lm_from_commits = p.lines && a.lm != c->d_lm;
-  // early-exit rounds with alive sets (liveness) take the SCAN_ALIVE variants
-  const bool alive_ee = a.alive && a.early_exit;
-  if (a.nloc > 0 && flat) {   // narrow rows: edge-parallel pull
-    p.kernel = PULL_FLAT;
-    p.mode = scan;
-  } else if (a.ulist && built(scan | SCAN_LIST)) {   // receiver-list round (launch_expand): waves for the listed vertices
-    p.kernel = PULL_LIST;
-    p.mode = scan | SCAN_LIST | (alive_ee ? SCAN_ALIVE : a.dprobe ? SCAN_DPROBE : 0);
-  } else if (a.nloc > 0 && unf) {
-    p.kernel = PULL_RECEIVER;
-    // The first aliasing round (alias without the done probe) runs the quads
-    // variant (done-neighbour receivers four at a time, low in-degree ones two
-    // at a time: profiles/r06_ab_alias_quads.txt), and so do the other
-    // unfiltered pulls once most messages are held: near-done rounds without
-    // liveness and, under liveness (parked rows), the alive early-exit pulls
-    // from the round that starts with half the messages held (C5 rounds 4-5;
-    // round 3, the dense one, keeps the plain alive variant:
-    // profiles/r06_ab_quads_c5.txt, r06_ab_gather_pairs.txt)
-    const bool half_held = (double)c->held_bits * 2.0 >= (double)c->n * (double)c->m;
-    if (alive_ee && built(scan | SCAN_ALIVE))
-      p.mode = scan | SCAN_ALIVE | (half_held && built(scan | SCAN_ALIVE | SCAN_QUADS) ? SCAN_QUADS : 0);
-    else if (a.dprobe && built(scan | SCAN_DPROBE)) p.mode = scan | SCAN_DPROBE;   // (done-probe rounds, launch_expand)
-    else if ((a.alias || a.near_done) && built(scan | SCAN_QUADS)) p.mode = scan | SCAN_QUADS;
-    else p.mode = scan;
-    // the packed gather: the plain pull, its serial loop's
-    // lanes dealt out over the live lines.  (Not the quads variant, whose
-    // receivers of in-degree <= 32 go through gather_pairs: with the serial
-    // loop alone packed it took 76 VGPRs against 72 and C4 round 4 ran 6.42 ->
-    // 7.14 ms, profiles/r11_ab_line_pack.txt)
-    if (c->line_pack_now && p.mode == scan && built(scan | SCAN_PACK)) p.mode |= SCAN_PACK;
-  } else if (a.nloc > 0) {
-    p.kernel = PULL_RECEIVER;
-    const int pre = c->prefilter_now ? SCAN_PRE : SCAN_FILTERED;
-    if (a.dprobe && built(scan | SCAN_DPROBE)) {
-      p.mode = scan | SCAN_DPROBE;
-    } else if (p.masked) {
-      p.mode = SCAN_MASKED;
-    } else if ((a.cmk || a.cmk_next) && built(pre | SCAN_CML)) {   // compact Message-Lists read and / or written
-      if (a.cmk && !a.early_exit && !c->prefilter_now && !a.alive) p.kernel = PULL_RECORD;
-      else p.mode = pre | SCAN_CML;
-    } else if (alive_ee && built(pre | SCAN_ALIVE)) {
-      p.mode = pre | SCAN_ALIVE;
-    } else if (p.lines) {
-      p.mode = SCAN_FILTERED | SCAN_LINES;
-    } else {
-      p.mode = pre;
-    }
-  }
-  return p;
 }
 
 // One pull round on the engine stream, with the hub chunks on the context's
@@ -572,7 +473,7 @@ static PullChoice choose_pull(const Ctx* c, const ExpandArgs& a, int W) {
 enum { PULL_OK = 0, PULL_NOT_BUILT = 1, PULL_ORDER_FAILED = 2 };
 template <int W>
 static int launch_expand_w(Ctx* c, ExpandArgs a) {
-  if (c->mode_push) {
+  if (c->plan.mode_push) {
     launch_push_w<W>(c, a);
     return PULL_OK;
   }
@@ -580,7 +481,7 @@ static int launch_expand_w(Ctx* c, ExpandArgs a) {
   if (a.unfiltered) launch_fixup_rows_w<W>(c);
   // (k_line_done reads the rows as they are now: after the last round's k_hub_final, before the fork)
   if (a.ldone) launch_line_done(c);
-  const PullChoice p = choose_pull(c, a, W);
+  const PullChoice& p = c->plan.pull;   // (round_plan.h: the kernel, its MODE, its pre-passes)
   if (p.masked) launch_arcmask(c);
   // kernel_ms (ev[4] .. ev[5]) brackets every kernel of the round's pull: the
   // degree-split push half and accumulator clear too (their accumulator
@@ -589,17 +490,13 @@ static int launch_expand_w(Ctx* c, ExpandArgs a) {
   if (a.prehi) launch_split_push_w<W>(c, a);   // degree-split round, push half: senders of in-degree < split_deg
   // line masks of the senders' rows (inside the pull's events and bytes)
   if (p.lines && !p.lm_from_commits) launch_mklm(c, a);   // (the last round's commits did not write them)
-  if (p.mode & SCAN_LINES) {
-    c->lines_ran = true;
-    c->lines_from_commits = p.lm_from_commits;
-  }
   const bool hubs = c->n_hub_items > 0;
   bool order_ok = true;
   if (hubs) {   // fork: the chunks first, their chains are the round's longest
     order_ok = hipEventRecord(c->ev_fork, c->stream) == hipSuccess &&
                hipStreamWaitEvent(c->side, c->ev_fork, 0) == hipSuccess;
     if (order_ok) {
-      launch_hub_partial_w<W>(c, a, a.unfiltered != 0, c->lines_ran, c->side);
+      launch_hub_partial_w<W>(c, a, a.unfiltered != 0, (p.mode & SCAN_LINES) != 0, c->side);
       order_ok = hipEventRecord(c->ev_join, c->side) == hipSuccess;
     }
   }

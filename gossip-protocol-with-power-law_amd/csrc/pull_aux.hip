@@ -127,12 +127,12 @@ __global__ __launch_bounds__(BLOCK) void k_unalias(uint8_t* __restrict__ sp, uin
 }
 
 int unalias(Ctx* c, bool senders_only) {
-  if (!c->alias_active) return 0;
+  if (!c->carry.alias_active) return 0;
   hipLaunchKernelGGL(k_unalias, dim3(std::min(grid_for((c->n_alloc + 63) / 64, WAVES), c->cu_count * 8 * GS)),
                      dim3(BLOCK), 0, c->stream, c->d_sp, c->d_ws, senders_only ? c->d_abits : nullptr,
                      c->d_midx, c->d_cmask, c->d_slot[c->cur], c->cur, c->n_alloc, c->words);
   GP_HIP(hipGetLastError());
-  if (!senders_only) c->alias_active = false;
+  if (!senders_only) c->carry.alias_active = false;
   return 0;
 }
 

@@ -374,7 +374,7 @@ void launch_push_w(Ctx* c, ExpandArgs a) {
   constexpr bool lanes = W <= GP_PUSH_LANES_MAXW;
   // the bitmap pays once the push has many arcs (a pass over n vertices
   // against three scattered loads per arc)
-  if (lanes && c->push_est * 16.0 >= (double)c->n_alloc) {
+  if (lanes && c->plan.push_est * 16.0 >= (double)c->n_alloc) {
     hipLaunchKernelGGL(k_mkneed, dim3(std::max(1, std::min(grid_for(c->n_alloc, BLOCK), c->cu_count * 8 * GS))),
                        dim3(BLOCK), 0, s, c->d_state, c->d_seenpop, c->d_done_at, a.vbegin, a.nloc, c->n_alloc,
                        c->d_nbits);

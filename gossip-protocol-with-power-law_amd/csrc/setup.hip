@@ -238,7 +238,6 @@ static void free_rows(Ctx* c) {
 
 static void free_state(Ctx* c) {
   dfree(&c->d_slot[2]);
-  c->park_failed = false;
   free_rows(c);
   for (int k = 0; k < 2; ++k) {
     dfree(&c->d_frx[k]);
@@ -246,7 +245,6 @@ static void free_state(Ctx* c) {
   }
   dfree(&c->d_sp); dfree(&c->d_ws); dfree(&c->d_ldone);
   dfree(&c->d_ulist[0]); dfree(&c->d_ulist[1]);
-  c->ulist_valid = false;
   dfree(&c->d_seenpop); dfree(&c->d_first); dfree(&c->d_digest);
   (void)curve_alloc(c, false);
   c->curve_on = false;
@@ -340,7 +338,7 @@ static int alloc_state(Ctx* c) {
   // ghost's slot row is its frontier); the spread curve counts them too
   c->frx_rows = c->local ? c->nloc() : (c->cfg.track_msg_forwards || c->curve_want ? c->n_alloc : 0);
   dfree(&c->d_slot[2]);   // (re)allocated at the first parking, for this W
-  c->park_failed = false;
+  c->carry = RoundCarry{};   // (new buffers carry nothing over; parking may be tried again)
   // S[0] | S[1] | accumulator rows of the owned receivers, one allocation
   free_rows(c);
   GP_TRY(dalloc(&c->d_rows, (2 * na + nl) * W));
@@ -891,10 +889,10 @@ int gp_reset(gp_ctx* c) {
   c->prev_new_bits = 0;
   c->prev_receivers = 0;
   c->held_bits = 0;
-  c->cml_written_prev = false;
-  c->cml_read_now = c->cml_write_now = false;
-  c->lm_written_prev = c->lm_write_now = false;
-  c->sate_since = -1;
+  // (a run starts with nothing carried: no records, line masks, aliases or
+  // receiver list, no sated vertex -- and parking untried)
+  c->carry = RoundCarry{};
+  c->plan = RoundPlan{};
   GP_HIP(hipMemsetAsync(c->d_miss, 0, na, s));
   GP_HIP(hipMemsetAsync(c->d_deg_live, 0, na * 4, s));
   GP_HIP(hipMemcpyAsync(c->d_deg_live, c->d_deg_out, (size_t)c->n_alloc * 4, hipMemcpyDeviceToDevice, s));
@@ -908,8 +906,6 @@ int gp_reset(gp_ctx* c) {
   c->pending_crash = false;
   c->msg_forwards_valid = true;
   c->last_reports = 0;
-  c->alias_active = c->alias_now = c->dprobe_now = false;
-  c->ulist_valid = c->ulist_emit_now = c->ulist_read_now = false;
   shard_reset(c);
   GP_TRY(curve_reset(c));
   GP_HIP(hipStreamSynchronize(s));

@@ -12,8 +12,12 @@ counters, Message-Lists, first receipts, digests, coverage, forwards, reports.
 A missing fork or join shows as a cycle that differs.  The reference's send
 loop and Message-List dedup: Peer.py:402-404, Peer.py:175-216.
 """
+import json
+
 import numpy as np
 import pytest
+
+import round_trace
 
 pytestmark = pytest.mark.gpu
 
@@ -110,13 +114,35 @@ def test_hubs_in_every_kind_of_round_repeated(pkg, wide, wide_ref):
     assert all(s["mode"] == 0 for s in st)
     assert any(s["scan"] & 32 for s in st), "no degree-split round"
     assert any(s["scan"] & 8 for s in st), "no line-mask round"
-    # unfiltered, early exit by the dense-frontier rule of launch_expand (last
+    # unfiltered, early exit by the dense-frontier rule of round_plan.h (last
     # round's new bits >= n * m / 16), before any alias: no done probe
     assert any((s["scan"] & 3) == 2 and not s["scan"] & 64 and p["new_bits"] * 16 >= nm
                for p, s in zip(st, st[1:])), "no unfiltered early-exit round"
     assert any(s["aliased"] > 0 for s in st), "no aliasing round"
     assert any(s["scan"] & 64 for s in st), "no done-probe round"
     assert any(s["scan"] & 128 for s in st), "no list round"
+
+
+@pytest.mark.parametrize("name", ["a", "b", "c", "d"])
+def test_rounds_as_recorded(pkg, wide, name):
+    """The round's plan is a pure function (csrc/round_plan.h) since the runs
+    of tests/golden/round_plan_trace.json were recorded, with the library of
+    the commit before: the same runs (tests/round_trace.py: this overlay plain,
+    under churn, at W = 8 with the default push_ratio, with compact records)
+    give every round's record again -- mode, scan, every counter, all but the
+    timings.  (The work counters too: on this overlay they repeated exactly in
+    every recording, the parent's and this tree's.)"""
+    g, origin = wide
+    assert round_trace.BASE == _cfg() and round_trace.N_WIDE == N_WIDE
+    want = next(e for e in json.load(open(round_trace.FIXTURE)) if e["name"] == name)
+    got = json.loads(json.dumps(round_trace.record(pkg, g, origin, name)))
+    assert sorted(got) == sorted(want)
+    for k in want:
+        if k != "rounds":
+            assert got[k] == want[k], k
+    assert len(got["rounds"]) == len(want["rounds"])
+    for a, b in zip(got["rounds"], want["rounds"]):
+        assert a == b, (a["round"], {k: (a[k], b[k]) for k in b if a[k] != b[k]})
 
 
 def test_hubs_under_churn(pkg, oracle, wide):
