@@ -240,6 +240,7 @@ int gp_checkpoint_load(gp_ctx* c, const void* host, int64_t bytes) {
   // the spread curve is not in the blob (as the job record): a
   // run restored at round 0 has counted nothing yet and keeps the cleared one
   if (h.round > 0) c->curve_valid = false;
+  load_restored(c, h.round);   // (nor the per-peer loads of an eager run, load.hip)
   return 0;
 }
 

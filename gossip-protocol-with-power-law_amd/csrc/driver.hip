@@ -321,6 +321,22 @@ __global__ __launch_bounds__(BLOCK) void k_bitsum(BitsumArgs a) {
   }
 }
 
+// The activity bitmap of fpop[cur] (and its summary level) ahead of
+// launch_expand, which builds both again from the same counts before anything
+// else reads them: the per-round traffic pass probes them at its hook (load.hip)
+int launch_activity_bits(Ctx* c, bool summary) {
+  hipLaunchKernelGGL(k_mkbits, dim3(std::max(1, std::min(grid_for(c->n_alloc, BLOCK), c->cu_count * 8 * GS))),
+                     dim3(BLOCK), 0, c->stream, c->d_fpop[c->cur], c->d_abits, c->n_alloc, c->d_seenpop,
+                     c->d_done_at, (u64*)nullptr, (const uint8_t*)nullptr, (const int32_t*)nullptr, c->d_stats + 64);
+  if (summary) {
+    const int64_t nwords = (c->n_alloc + 63) / 64;
+    hipLaunchKernelGGL(k_mksum, dim3(grid_for((nwords + 63) / 64, WAVES)), dim3(BLOCK), 0, c->stream, c->d_abits,
+                       c->d_sbits, nwords);
+  }
+  GP_HIP(hipGetLastError());
+  return 0;
+}
+
 // the pull's argument block for this round's plan
 static void fill_expand(Ctx* c, ExpandArgs& a) {
   const RoundPlan& p = c->plan;
@@ -589,6 +605,7 @@ static int round_launch(Ctx* c) {
     b.count = c->nloc();
     GP_TRY(launch_bitsum(c, b, false, true));
   }
+  GP_TRY(load_count_round(c));   // (nothing is launched unless gp_track_load is on and the run counts per round)
 
   GP_HIP(hipEventRecord(c->ev[1], s));
   GP_TRY(launch_expand(c));
@@ -967,6 +984,14 @@ int gp_read(gp_ctx* c, int32_t what, void* host, int64_t bytes) {
         if (!fp[v]) std::memset(h + v * W, 0, (size_t)W * 8);
       return 0;
     }
+    case GP_LOAD_SENT:
+    case GP_LOAD_RECV:   // per-peer traffic record (load.hip)
+      return load_read(c, what, host, bytes);
+    case GP_SEENPOP:
+      if (!run) return set_error(GP_ESTATE, "no run state");
+      GP_TRY(need(nl * 4));
+      if (bytes) GP_TRY(copy_sync(c, host, c->d_seenpop, (size_t)bytes, hipMemcpyDeviceToHost));
+      return 0;
     default:
       return set_error(GP_EINVAL, "unknown gp_what");
   }

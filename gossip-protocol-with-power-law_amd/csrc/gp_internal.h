@@ -148,6 +148,16 @@ struct Ctx {
   bool curve_want = false, curve_alloc = false, curve_on = false, curve_valid = false;
   int curve_grid = 0;                     // GP_CURVE_GRID at gp_create: cap of k_curve's grid (0: none)
   bool curve_yard = false;                // GP_CURVE_YARDSTICK=1 at gp_create: time k_curve beside k_bitsum
+  // per-peer traffic record (load.hip): lines sent / received
+  // per vertex since gp_reset, and the lazy read's scratch (x = seenpop - fpop).
+  // load_want is what gp_track_load asked for, load_on what the run since the
+  // last gp_reset keeps (single-rank contexts only); load_valid falls when a
+  // checkpoint restores an eager run past round 0 (the totals are not in the blob)
+  u64* d_load_sent = nullptr;             // [n]
+  u64* d_load_recv = nullptr;             // [n]
+  uint32_t* d_load_x = nullptr;           // [n]
+  bool load_want = false, load_on = false, load_valid = false;
+  bool load_force = false;                // GP_LOAD_EAGER=1 at gp_create: count per round from round 0
   bool holds_frx() const { return cfg.track_msg_forwards != 0 || local || curve_want; }
   uint32_t* d_fpop[2] = {nullptr, nullptr};    // [n_alloc]
   int cur = 0;
@@ -371,6 +381,16 @@ int curve_reset(Ctx* c);                       // new run: cleared, counted from
 int curve_count_round(Ctx* c);                 // after E_r: rows r (injections) and r + 1 (first receipts)
 int curve_env_grid();                          // GP_CURVE_GRID in the environment (0: unset)
 bool curve_env_yardstick();                    // GP_CURVE_YARDSTICK=1 in the environment
+// load.hip
+int load_reset(Ctx* c);                        // gp_reset: gp_track_load takes effect; buffers (or none), cleared
+void load_free(Ctx* c);
+int load_count_round(Ctx* c);                  // after L_r and I_r of an eager run: round r's sends and arrivals
+int load_before_liveness(Ctx* c);              // gp_crash turns liveness on: a lazy run books its rounds so far
+void load_restored(Ctx* c, int32_t round);     // gp_checkpoint_load: an eager run past round 0 lost its totals
+int load_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_LOAD_SENT / GP_LOAD_RECV
+bool load_env_eager();                         // GP_LOAD_EAGER=1 in the environment
+// driver.hip: k_mkbits (and k_mksum) over fpop[cur], ahead of launch_expand
+int launch_activity_bits(Ctx* c, bool summary);
 // driver.hip: cnt[m] += the rows' bit m over rows [0, count) with guard[i] != 0 (the per-bit k_bitsum)
 int bitsum_count_rows(Ctx* c, const u64* rows, const uint32_t* guard, int64_t count, u64* cnt);
 // partition.hip

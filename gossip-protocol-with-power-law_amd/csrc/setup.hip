@@ -248,6 +248,7 @@ static void free_state(Ctx* c) {
   dfree(&c->d_seenpop); dfree(&c->d_first); dfree(&c->d_digest);
   (void)curve_alloc(c, false);
   c->curve_on = false;
+  load_free(c);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_abits); dfree(&c->d_dbits); dfree(&c->d_lm); dfree(&c->d_lmw[0]); dfree(&c->d_lmw[1]); dfree(&c->d_sbits); dfree(&c->d_amask); dfree(&c->d_cml[0]); dfree(&c->d_cml[1]); dfree(&c->d_cmk[0]); dfree(&c->d_cmk[1]); dfree(&c->d_done_at);
@@ -547,6 +548,7 @@ int gp_create(int device, gp_ctx** out) {
   if (const char* e = getenv("GP_LINE_PACK")) c->lp_env = e[0] == '1' ? 1 : e[0] == '0' ? 0 : -1;
   c->curve_grid = curve_env_grid();   // (a test lever, as GP_FINALIZE_ROWS: few blocks fill k_curve's planes)
   c->curve_yard = curve_env_yardstick();
+  c->load_force = load_env_eager();   // (a test lever: the per-round traffic pass from round 0, load.hip)
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->cu_count = prop.multiProcessorCount;
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -594,6 +596,7 @@ void gp_destroy(gp_ctx* c) {
   dfree(&c->d_sp); dfree(&c->d_ws); dfree(&c->d_ldone); dfree(&c->d_ld_cand);
   dfree(&c->d_ulist[0]); dfree(&c->d_ulist[1]);
   dfree(&c->d_seenpop); dfree(&c->d_first); dfree(&c->d_digest); dfree(&c->d_curve);
+  load_free(c);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_stats);
@@ -908,6 +911,7 @@ int gp_reset(gp_ctx* c) {
   c->last_reports = 0;
   shard_reset(c);
   GP_TRY(curve_reset(c));
+  GP_TRY(load_reset(c));   // (gp_track_load takes effect here)
   GP_HIP(hipStreamSynchronize(s));
   return 0;
 }
@@ -921,6 +925,7 @@ int gp_crash(gp_ctx* c, int32_t nverts, const int32_t* verts) {
   // global ids; a partitioned context applies the crashes of the vertices it
   // holds (owned, ghosts, origins) -- the others never touch its slice
   GP_TRY(unalias(c, false));   // (liveness turns on: the run's rounds can no longer keep aliases)
+  if (nverts > 0 && !c->liveness_active) GP_TRY(load_before_liveness(c));   // (before the crash is applied)
   std::vector<uint8_t> st((size_t)c->n_alloc);
   GP_HIP(hipStreamSynchronize(c->stream));
   GP_TRY(copy_sync(c, st.data(), c->d_state, (size_t)c->n_alloc, hipMemcpyDeviceToHost));

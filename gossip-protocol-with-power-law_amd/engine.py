@@ -394,6 +394,26 @@ class GossipEngine:
         """The whole shard job's curve after combine(): u64 [job rounds + 1][m_total]."""
         return self._read_curve(1, m_total)
 
+    # -- per-peer traffic record (csrc/load.hip; helpers in load.py) --------
+    def track_load(self, on=True):
+        """gp_track_load: keep the gossip lines every peer sent and received
+        (duplicates included) from the next reset() on."""
+        check(self._lib.gp_track_load(self._ctx, 1 if on else 0))
+
+    def load_sent(self):
+        """u64 [n]: lines peer u put on the wire since reset(), over all its
+        links; sums to the rounds' `sends`."""
+        return self._read(_lib.LOAD_SENT, np.empty(self.n, dtype=np.uint64))
+
+    def load_recv(self):
+        """u64 [n]: lines that arrived at peer v since reset(), duplicates
+        included (load.duplicates turns them into duplicates alone)."""
+        return self._read(_lib.LOAD_RECV, np.empty(self.n, dtype=np.uint64))
+
+    def seenpop(self):
+        """u32 per owned vertex: |Message-List(v)|, the messages v holds."""
+        return self._read(_lib.SEENPOP, np.empty(self.nloc(), dtype=np.uint32))
+
     def _nv(self):   # per-vertex reads: the owned slice of a partitioned context
         return self.nloc() if self.nranks > 1 else self.n
 

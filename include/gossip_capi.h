@@ -186,7 +186,12 @@ typedef enum gp_what {
   /* the whole job of a message-shard run, after gp_shard_combine (else GP_ESTATE) */
   GP_JOB_DIGEST = 13,   /* u64 [n]        per-vertex digest of every shard's messages    */
   GP_JOB_COVERAGE = 14, /* u64 [m_total]  vertices holding message k of the job table    */
-  GP_JOB_FORWARDS = 15  /* u64 [m_total]  sends of message k (GP_ENOTRACK as GP_FORWARDS) */
+  GP_JOB_FORWARDS = 15, /* u64 [m_total]  sends of message k (GP_ENOTRACK as GP_FORWARDS) */
+  /* per-peer traffic record (gp_track_load below) */
+  GP_LOAD_SENT = 16,  /* u64 [n]  gossip lines peer u sent, over all its links       */
+  GP_LOAD_RECV = 17,  /* u64 [n]  gossip lines that arrived at peer v, duplicates too */
+  GP_SEENPOP = 18     /* u32 [vend-vbegin]  |Message-List(v)|: the messages v holds
+                         (readable without tracking; exact for aliased vertices)   */
 } gp_what;
 
 int gp_abi_version(void);
@@ -318,6 +323,45 @@ int gp_shard_combine(gp_ctx* ctx, gp_round_stats* job, int32_t cap, int32_t* rou
  * rank tracked a valid curve.  GP_EINVAL if cap_rows < rows: nothing is written. */
 int gp_track_curve(gp_ctx* ctx, int32_t on);
 int gp_read_curve(gp_ctx* ctx, int32_t job, uint64_t* host, int32_t cap_rows, int32_t* rows_out);
+
+/* Per-peer traffic record: the totals of what every
+ * reference peer logs line by line -- Peer.py:206 and Peer.py:286 log each
+ * arriving message with the peer it came from, duplicate or not, and
+ * Peer.py:402-404 send on every outgoing link.  Over the rounds run since
+ * gp_reset, with frontier_r(u) u's frontier after the liveness and injection
+ * phases of round r (empty for a vertex that is down):
+ *   GP_LOAD_SENT  sent[u] = sum_r max(deg_live_r(u), 0) * |frontier_r(u)|, the
+ *                 sends gp_round_stats.sends counts, per sender: the array sums
+ *                 to the sum of the rounds' sends exactly;
+ *   GP_LOAD_RECV  recv[v] = sum_r [v up in round r] * sum_{u in In(v)}
+ *                 |frontier_r(u)|.  A send to a crashed, not yet removed peer is
+ *                 attempted: it counts in sent and is received by nobody; a
+ *                 link to a removed peer carries nothing.  So sum recv <= sum
+ *                 sent, with equality when no vertex is ever down.
+ * recv[v] - (GP_SEENPOP[v] - messages injected at v) are v's duplicate arrivals.
+ * Both are readable between rounds.  A context that runs a block of a message
+ * table (msg_word_base) holds the totals of its own messages: the arrays of a
+ * job's shards add up to the whole run's (the host adds them; gp_shard_combine
+ * does not).
+ *
+ * gp_track_load(on) takes effect at the next gp_reset, which allocates (and
+ * clears) two u64[n] and one u32[n]; off, nothing is allocated or launched.
+ * While no vertex has ever been down the rounds launch nothing either: a read
+ * computes the totals from the run's state (every message a vertex holds was in
+ * its frontier exactly once), one pass over the in-CSR.  With churn, or from
+ * the first gp_crash on (which books the rounds so far before it is applied),
+ * every round adds its own pass before the expansion (round_ms carries it;
+ * expand_ms and kernel_ms keep their meaning).  GP_LOAD_EAGER=1 in the
+ * environment at gp_create counts per round from round 0 (a test lever).
+ * Tracking changes no other output.
+ *
+ * Reads: GP_ENOTRACK before tracking took effect, and on a vertex-partitioned
+ * context (nranks > 1: ghosts keep no frontier counts -- not supported);
+ * GP_ESTATE for a run that counts per round and was restored from a checkpoint
+ * past round 0 (the blob does not hold the totals), until the next gp_reset.  A
+ * restored run that never had a vertex down reads correctly: its totals are a
+ * function of the restored state. */
+int gp_track_load(gp_ctx* ctx, int32_t on);
 
 /* Checkpoints (no reference counterpart -- the
  * reference's peers keep no state across restarts).  Taken between rounds:
