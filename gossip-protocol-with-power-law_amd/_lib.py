@@ -26,6 +26,7 @@ GP_OK, GP_EINVAL, GP_EHIP, GP_ENOMEM, GP_ESTATE, GP_ERCCL, GP_ENOTRACK = 0, -1, 
 SEEN, FIRST, DIGEST, COVERAGE, FORWARDS, STATE, MISS, DEG_LIVE, ROW_PTR, COL, FRONTIER, FPOP, L2G = range(13)
 JOB_DIGEST, JOB_COVERAGE, JOB_FORWARDS = 13, 14, 15   # after gp_shard_combine
 LOAD_SENT, LOAD_RECV, SEENPOP = 16, 17, 18            # per-peer traffic record (gp_track_load), |Message-List|
+FRESH_SENT, FRESH_RECV = 19, 20                       # per-peer fresh deliveries (gp_track_fresh)
 # gp_shard_info transports
 XPORT_NONE, XPORT_RCCL, XPORT_HOST = 0, 1, 2
 
@@ -140,6 +141,7 @@ SIGNATURES = {
     "gp_track_curve": (ctypes.c_int, [_P, _I32]),
     "gp_read_curve": (ctypes.c_int, [_P, _I32, _P, _I32, _PI32]),
     "gp_track_load": (ctypes.c_int, [_P, _I32]),
+    "gp_track_fresh": (ctypes.c_int, [_P, _I32]),
     "gp_checkpoint_size": (ctypes.c_int, [_P, _PI64]),
     "gp_checkpoint_save": (ctypes.c_int, [_P, _P, _I64]),
     "gp_checkpoint_load": (ctypes.c_int, [_P, _P, _I64]),

@@ -364,7 +364,11 @@ static void fill_expand(Ctx* c, ExpandArgs& a) {
   a.cml = p.cml_read ? c->d_cml[c->cur] : nullptr;
   a.cmk_next = p.cml_write ? c->d_cmk[c->cur ^ 1] : nullptr;
   a.cml_next = p.cml_write ? c->d_cml[c->cur ^ 1] : nullptr;
-  a.frx = c->d_frx[0] ? c->d_frx[c->cur] : nullptr;
+  // (the push reads the senders' exact rows where some other output keeps them;
+  // rows kept for gp_track_fresh alone leave its source, and so every work
+  // counter of the run, the untracked run's)
+  const bool frx_src = c->cfg.track_msg_forwards != 0 || c->local || c->curve_want;
+  a.frx = c->d_frx[0] && frx_src ? c->d_frx[c->cur] : nullptr;
   a.frx_next = c->d_frx[0] ? c->d_frx[c->cur ^ 1] : nullptr;
   a.frx_rows = c->frx_rows;
   a.done_at = c->d_done_at;
@@ -612,7 +616,8 @@ static int round_launch(Ctx* c) {
   hipLaunchKernelGGL(k_stats_reduce, dim3(NST), dim3(BLOCK), 0, s, partial, stats);
   GP_HIP(hipGetLastError());
   GP_HIP(hipEventRecord(c->ev[2], s));
-  return curve_count_round(c);   // (nothing is launched unless gp_track_curve is on)
+  GP_TRY(curve_count_round(c));   // (nothing is launched unless gp_track_curve is on)
+  return fresh_count_round(c);    // (... gp_track_fresh; both after expand_ms ends: round_ms carries them)
 }
 
 // X_r over RCCL.  One rank: the counters' all-reduce is the whole exchange.
@@ -987,6 +992,9 @@ int gp_read(gp_ctx* c, int32_t what, void* host, int64_t bytes) {
     case GP_LOAD_SENT:
     case GP_LOAD_RECV:   // per-peer traffic record (load.hip)
       return load_read(c, what, host, bytes);
+    case GP_FRESH_SENT:
+    case GP_FRESH_RECV:   // per-peer fresh deliveries (fresh.hip)
+      return fresh_read(c, what, host, bytes);
     case GP_SEENPOP:
       if (!run) return set_error(GP_ESTATE, "no run state");
       GP_TRY(need(nl * 4));

@@ -137,7 +137,7 @@ struct Ctx {
   // (carry.park_failed: it could not be)
   uint8_t* d_sp = nullptr;          // [n_alloc] slot of v's seen row (0xFF: none)
   uint8_t* d_ws = nullptr;          // [n_alloc] bit p: slot p written this run
-  u64* d_frx[2] = {nullptr, nullptr};     // exact frontier rows (track_msg_forwards; partitioned; spread curve)
+  u64* d_frx[2] = {nullptr, nullptr};     // exact frontier rows (track_msg_forwards; partitioned; spread curve; fresh deliveries)
   int64_t frx_rows = 0;                   // rows d_frx covers (partitioned: the owned ones)
   // spread curve (curve.hip): [255][W * 64] first receipts per
   // receipt round and message over the owned vertices.  curve_want is what
@@ -158,7 +158,17 @@ struct Ctx {
   uint32_t* d_load_x = nullptr;           // [n]
   bool load_want = false, load_on = false, load_valid = false;
   bool load_force = false;                // GP_LOAD_EAGER=1 at gp_create: count per round from round 0
-  bool holds_frx() const { return cfg.track_msg_forwards != 0 || local || curve_want; }
+  // per-peer fresh deliveries (fresh.hip): of those lines, the
+  // ones that carried a first receipt, per sender and per receiver since
+  // gp_reset.  fresh_want is what gp_track_fresh asked for, fresh_alloc what
+  // alloc_state sized the frontier rows for, fresh_on what the run since the
+  // last gp_reset keeps (single-rank contexts only); fresh_valid falls when a
+  // checkpoint restores the run past round 0 (the totals are not in the blob)
+  u64* d_fresh_sent = nullptr;            // [n]
+  u64* d_fresh_recv = nullptr;            // [n]
+  bool fresh_want = false, fresh_alloc = false, fresh_on = false, fresh_valid = false;
+  bool fresh_gather = false;              // GP_FRESH_GATHER=1 at gp_create: undirected overlays gather once per role
+  bool holds_frx() const { return cfg.track_msg_forwards != 0 || local || curve_want || fresh_want; }
   uint32_t* d_fpop[2] = {nullptr, nullptr};    // [n_alloc]
   int cur = 0;
   uint32_t* d_seenpop = nullptr;    // [nloc]
@@ -389,6 +399,13 @@ int load_before_liveness(Ctx* c);              // gp_crash turns liveness on: a 
 void load_restored(Ctx* c, int32_t round);     // gp_checkpoint_load: an eager run past round 0 lost its totals
 int load_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_LOAD_SENT / GP_LOAD_RECV
 bool load_env_eager();                         // GP_LOAD_EAGER=1 in the environment
+// fresh.hip
+int fresh_reset(Ctx* c);                       // gp_reset: gp_track_fresh takes effect; buffers (or none), cleared
+void fresh_free(Ctx* c);
+int fresh_count_round(Ctx* c);                 // after E_r: round r's first-receipt deliveries per sender / receiver
+void fresh_restored(Ctx* c, int32_t round);    // gp_checkpoint_load: a run past round 0 lost its totals
+int fresh_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_FRESH_SENT / GP_FRESH_RECV
+bool fresh_env_gather();                       // GP_FRESH_GATHER=1 in the environment
 // driver.hip: k_mkbits (and k_mksum) over fpop[cur], ahead of launch_expand
 int launch_activity_bits(Ctx* c, bool summary);
 // driver.hip: cnt[m] += the rows' bit m over rows [0, count) with guard[i] != 0 (the per-bit k_bitsum)

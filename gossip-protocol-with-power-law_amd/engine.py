@@ -414,6 +414,23 @@ class GossipEngine:
         """u32 per owned vertex: |Message-List(v)|, the messages v holds."""
         return self._read(_lib.SEENPOP, np.empty(self.nloc(), dtype=np.uint32))
 
+    # -- per-peer fresh deliveries (csrc/fresh.hip; helpers in redundancy.py) --
+    def track_fresh(self, on=True):
+        """gp_track_fresh: keep, per peer, the sends and arrivals that carried
+        a first receipt from the next reset() on."""
+        check(self._lib.gp_track_fresh(self._ctx, 1 if on else 0))
+
+    def fresh_sent(self):
+        """u64 [n]: peer u's sends since reset() that delivered a message the
+        receiver did not hold (load_sent() - fresh_sent(): its wasted sends)."""
+        return self._read(_lib.FRESH_SENT, np.empty(self.n, dtype=np.uint64))
+
+    def fresh_recv(self):
+        """u64 [n]: arrivals at peer v since reset() of a message it did not
+        hold at the start of the round (load_recv() - fresh_recv(): its stale
+        arrivals)."""
+        return self._read(_lib.FRESH_RECV, np.empty(self.n, dtype=np.uint64))
+
     def _nv(self):   # per-vertex reads: the owned slice of a partitioned context
         return self.nloc() if self.nranks > 1 else self.n
 

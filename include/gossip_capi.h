@@ -190,8 +190,11 @@ typedef enum gp_what {
   /* per-peer traffic record (gp_track_load below) */
   GP_LOAD_SENT = 16,  /* u64 [n]  gossip lines peer u sent, over all its links       */
   GP_LOAD_RECV = 17,  /* u64 [n]  gossip lines that arrived at peer v, duplicates too */
-  GP_SEENPOP = 18     /* u32 [vend-vbegin]  |Message-List(v)|: the messages v holds
+  GP_SEENPOP = 18,    /* u32 [vend-vbegin]  |Message-List(v)|: the messages v holds
                          (readable without tracking; exact for aliased vertices)   */
+  /* per-peer fresh deliveries (gp_track_fresh below) */
+  GP_FRESH_SENT = 19, /* u64 [n]  peer u's sends that delivered a first receipt      */
+  GP_FRESH_RECV = 20  /* u64 [n]  arrivals at peer v of a message it did not hold    */
 } gp_what;
 
 int gp_abi_version(void);
@@ -362,6 +365,50 @@ int gp_read_curve(gp_ctx* ctx, int32_t job, uint64_t* host, int32_t cap_rows, in
  * restored run that never had a vertex down reads correctly: its totals are a
  * function of the restored state. */
 int gp_track_load(gp_ctx* ctx, int32_t on);
+
+/* Per-peer fresh deliveries: of the lines the traffic
+ * record counts, the ones that told the receiver something it did not hold --
+ * what one reads a gossip log (Peer.py:206, Peer.py:286: every arrival with
+ * the peer it came from) for.  With frontier_r(u) as above and new_r(v) the
+ * messages v first receives in the expansion of round r (receipt round r + 1),
+ * over the rounds run since gp_reset:
+ *   GP_FRESH_SENT  fresh_sent[u] = sum_r sum_{v in Out(u)} |frontier_r(u) & new_r(v)|,
+ *                  u's sends that delivered a first receipt;
+ *   GP_FRESH_RECV  fresh_recv[v] = sum_r sum_{u in In(v)}  |frontier_r(u) & new_r(v)|,
+ *                  the arrivals at v of a message v did not hold at the start
+ *                  of the round.
+ * Several in-neighbours delivering one message in the same round all count:
+ * none was a duplicate when it was sent.  A down receiver has no new_r, a
+ * crashed sender's frontier is dropped, a removed peer is down.  So
+ *   sum fresh_sent = sum fresh_recv exactly;
+ *   fresh_sent[u] <= GP_LOAD_SENT[u] and fresh_recv[v] <= GP_LOAD_RECV[v]
+ *   (sent - fresh_sent: u's wasted sends; recv - fresh_recv: v's stale arrivals);
+ *   fresh_recv[v] >= GP_SEENPOP[v] - messages injected at v, with equality iff
+ *   every message reached v from one neighbour only;
+ *   per round, sum fresh_recv grows by at least gp_round_stats.new_bits.
+ * Both are pure functions of the first-receipt matrix: arc u -> v contributes
+ * the messages m with first[v][m] = first[u][m] + 1 and u up in round
+ * first[u][m].  Readable between rounds.  A context that runs a block of a
+ * message table (msg_word_base) holds the totals of its own messages: the
+ * arrays of a job's shards add up to the whole run's (the host adds them;
+ * gp_shard_combine does not).
+ *
+ * gp_track_fresh(on) takes effect at the next gp_reset, which makes the exact
+ * frontier rows exist (the buffers track_msg_forwards and gp_track_curve keep,
+ * shared when several are on) and allocates (and clears) two u64[n]; off,
+ * nothing is allocated or launched.  Every round then adds one pass after the
+ * expansion (round_ms carries it; expand_ms and kernel_ms keep their meaning).
+ * Tracking changes no other output and no counter; it does not make
+ * GP_FRONTIER or GP_FORWARDS readable and does not turn on the per-round
+ * forwards pass.  GP_FRESH_GATHER=1 in the environment at gp_create runs
+ * undirected overlays through the pass's other form, one gather per role and
+ * no per-arc atomics (a measurement lever; the totals are the same).
+ *
+ * Reads: GP_ENOTRACK before tracking took effect, and on a vertex-partitioned
+ * context (nranks > 1: not supported); GP_ESTATE for a run restored from a
+ * checkpoint past round 0 (the blob does not hold the totals, and they are no
+ * function of the restored state), until the next gp_reset. */
+int gp_track_fresh(gp_ctx* ctx, int32_t on);
 
 /* Checkpoints (no reference counterpart -- the
  * reference's peers keep no state across restarts).  Taken between rounds:
