@@ -142,6 +142,8 @@ SIGNATURES = {
     "gp_read_curve": (ctypes.c_int, [_P, _I32, _P, _I32, _PI32]),
     "gp_track_load": (ctypes.c_int, [_P, _I32]),
     "gp_track_fresh": (ctypes.c_int, [_P, _I32]),
+    "gp_track_fresh_curve": (ctypes.c_int, [_P, _I32]),
+    "gp_read_fresh_curve": (ctypes.c_int, [_P, _P, _I32, _PI32]),
     "gp_checkpoint_size": (ctypes.c_int, [_P, _PI64]),
     "gp_checkpoint_save": (ctypes.c_int, [_P, _P, _I64]),
     "gp_checkpoint_load": (ctypes.c_int, [_P, _P, _I64]),

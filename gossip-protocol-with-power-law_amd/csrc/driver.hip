@@ -365,7 +365,7 @@ static void fill_expand(Ctx* c, ExpandArgs& a) {
   a.cmk_next = p.cml_write ? c->d_cmk[c->cur ^ 1] : nullptr;
   a.cml_next = p.cml_write ? c->d_cml[c->cur ^ 1] : nullptr;
   // (the push reads the senders' exact rows where some other output keeps them;
-  // rows kept for gp_track_fresh alone leave its source, and so every work
+  // rows kept for gp_track_fresh or gp_track_fresh_curve alone leave its source, and so every work
   // counter of the run, the untracked run's)
   const bool frx_src = c->cfg.track_msg_forwards != 0 || c->local || c->curve_want;
   a.frx = c->d_frx[0] && frx_src ? c->d_frx[c->cur] : nullptr;
@@ -617,7 +617,8 @@ static int round_launch(Ctx* c) {
   GP_HIP(hipGetLastError());
   GP_HIP(hipEventRecord(c->ev[2], s));
   GP_TRY(curve_count_round(c));   // (nothing is launched unless gp_track_curve is on)
-  return fresh_count_round(c);    // (... gp_track_fresh; both after expand_ms ends: round_ms carries them)
+  GP_TRY(fresh_count_round(c));   // (... gp_track_fresh)
+  return fresh_curve_count_round(c);   // (... gp_track_fresh_curve; all after expand_ms ends: round_ms carries them)
 }
 
 // X_r over RCCL.  One rank: the counters' all-reduce is the whole exchange.

@@ -168,7 +168,19 @@ struct Ctx {
   u64* d_fresh_recv = nullptr;            // [n]
   bool fresh_want = false, fresh_alloc = false, fresh_on = false, fresh_valid = false;
   bool fresh_gather = false;              // GP_FRESH_GATHER=1 at gp_create: undirected overlays gather once per role
-  bool holds_frx() const { return cfg.track_msg_forwards != 0 || local || curve_want || fresh_want; }
+  // fresh-delivery curve (fresh_curve.hip): [255][W * 64] the
+  // deliverers of every message's first receipts per receipt round, the
+  // per-message split of fresh_recv.  The four flags are the fresh
+  // deliveries': what gp_track_fresh_curve asked for, what alloc_state sized
+  // the frontier rows for, what the run since the last gp_reset keeps
+  // (single-rank contexts only), and whether a restore past round 0 lost it
+  u64* d_fresh_curve = nullptr;
+  size_t fresh_curve_words = 0;           // u64 d_fresh_curve holds
+  bool fresh_curve_want = false, fresh_curve_alloc = false, fresh_curve_on = false, fresh_curve_valid = false;
+  int fresh_curve_grid = 0;               // GP_FRESH_CURVE_GRID at gp_create: cap of k_fresh_curve's grid (0: none)
+  bool holds_frx() const {
+    return cfg.track_msg_forwards != 0 || local || curve_want || fresh_want || fresh_curve_want;
+  }
   uint32_t* d_fpop[2] = {nullptr, nullptr};    // [n_alloc]
   int cur = 0;
   uint32_t* d_seenpop = nullptr;    // [nloc]
@@ -406,6 +418,12 @@ int fresh_count_round(Ctx* c);                 // after E_r: round r's first-rec
 void fresh_restored(Ctx* c, int32_t round);    // gp_checkpoint_load: a run past round 0 lost its totals
 int fresh_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_FRESH_SENT / GP_FRESH_RECV
 bool fresh_env_gather();                       // GP_FRESH_GATHER=1 in the environment
+// fresh_curve.hip
+int fresh_curve_reset(Ctx* c);                 // gp_reset: gp_track_fresh_curve takes effect; the record (or none), cleared
+void fresh_curve_free(Ctx* c);
+int fresh_curve_count_round(Ctx* c);           // after E_r: row r + 1, the deliverers of round r's first receipts
+void fresh_curve_restored(Ctx* c, int32_t round);   // gp_checkpoint_load: a run past round 0 lost its record
+int fresh_curve_env_grid();                    // GP_FRESH_CURVE_GRID in the environment (0: unset)
 // driver.hip: k_mkbits (and k_mksum) over fpop[cur], ahead of launch_expand
 int launch_activity_bits(Ctx* c, bool summary);
 // driver.hip: cnt[m] += the rows' bit m over rows [0, count) with guard[i] != 0 (the per-bit k_bitsum)

@@ -431,6 +431,21 @@ class GossipEngine:
         arrivals)."""
         return self._read(_lib.FRESH_RECV, np.empty(self.n, dtype=np.uint64))
 
+    # -- fresh-delivery curves (csrc/fresh_curve.hip; helpers in redundancy.py) --
+    def track_fresh_curve(self, on=True):
+        """gp_track_fresh_curve: count, per (receipt round, message), the sends
+        that delivered a first receipt from the next reset() on."""
+        check(self._lib.gp_track_fresh_curve(self._ctx, 1 if on else 0))
+
+    def fresh_curve(self):
+        """u64 [rounds run + 1][m]: fresh_curve[R][k] = the sends of message k
+        in round R - 1 that delivered a first receipt (row 0 is zero), the
+        deliverers behind curve()[R][k]; the columns are curve()'s."""
+        buf = np.zeros((255, int(self.m)), dtype=np.uint64)   # receipt rounds 0 .. 254
+        rows = ctypes.c_int32()
+        check(self._lib.gp_read_fresh_curve(self._ctx, _ptr(buf), buf.shape[0], ctypes.byref(rows)))
+        return buf[:rows.value].copy()
+
     def _nv(self):   # per-vertex reads: the owned slice of a partitioned context
         return self.nloc() if self.nranks > 1 else self.n
 

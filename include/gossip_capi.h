@@ -410,6 +410,53 @@ int gp_track_load(gp_ctx* ctx, int32_t on);
  * function of the restored state), until the next gp_reset. */
 int gp_track_fresh(gp_ctx* ctx, int32_t on);
 
+/* Fresh-delivery curves: the fresh deliveries split by
+ * message and round instead of by peer -- for message k in round r, how many
+ * of the sends that carried it delivered a first receipt.  With frontier_r(u)
+ * and new_r(v) as above,
+ *   fresh_curve[r + 1][k] = #{ arcs u -> v, u in In(v) : k in frontier_r(u) & new_r(v) }
+ *   fresh_curve[0][k]     = 0
+ * rows indexed by receipt round, so that they line up with the spread curve's:
+ * fresh_curve[R][k] / curve[R][k] is the deliverers per first receipt of
+ * message k at receipt round R.  Several in-neighbours delivering k to v in one
+ * round all count, with no tie-break; an injection has no deliverer; a down
+ * receiver has no new_r, a crashed sender's frontier is dropped, a removed peer
+ * is down.  So
+ *   the sum of row r + 1 is what sum GP_FRESH_RECV grows by in round r, exactly;
+ *   the column sums are the run's news deliveries of each message, and the
+ *   whole array sums to sum GP_FRESH_RECV = sum GP_FRESH_SENT;
+ *   fresh_curve[R][k] >= curve[R][k] - (injections of k at round R at an up
+ *   origin) for R >= 1: every expansion receipt has at least one deliverer;
+ *   fresh_curve[R][k] <= the sends of message k in round R - 1.
+ * It is a pure function of the first-receipt matrix: arc u -> v counts for
+ * column k at row first[u][k] + 1 iff first[u][k] != 255, first[v][k] =
+ * first[u][k] + 1 and u is up in round first[u][k].  A context that runs a
+ * block of a message table (msg_word_base) holds the columns of its own
+ * messages: the shards' arrays concatenate to the whole run's (the host does
+ * it; gp_shard_combine does not).
+ *
+ * gp_track_fresh_curve(on) takes effect at the next gp_reset, which makes the
+ * exact frontier rows exist (shared with track_msg_forwards, gp_track_curve and
+ * gp_track_fresh when several are on) and allocates (and clears) a [255][64W]
+ * u64 buffer; off, nothing is allocated or launched.  Every round then adds
+ * one pass after the expansion (round_ms carries it; expand_ms and kernel_ms
+ * keep their meaning); a round whose receipt round would be 255 or more is
+ * refused, as with gp_track_curve.  Tracking changes no other output and no
+ * counter, and makes neither GP_FRONTIER nor GP_FORWARDS readable.  An overlay
+ * of 2^32 arcs or more is refused at that gp_reset (GP_EINVAL).
+ * GP_FRESH_CURVE_GRID=blocks in the environment at gp_create caps the pass's
+ * grid (a test lever; the array is the same).
+ *
+ * gp_read_fresh_curve writes u64 [rows][m] (the m real columns) and *rows_out =
+ * rows = rounds run since gp_reset + 1.  Readable between rounds; a read
+ * changes nothing.  GP_EINVAL for a null argument or cap_rows < rows: nothing
+ * is written.  GP_ENOTRACK before tracking took effect, and on a vertex-
+ * partitioned context (nranks > 1: not supported); GP_ESTATE for a run restored
+ * from a checkpoint past round 0 (the blob does not hold the record), until the
+ * next gp_reset. */
+int gp_track_fresh_curve(gp_ctx* ctx, int32_t on);
+int gp_read_fresh_curve(gp_ctx* ctx, uint64_t* host, int32_t cap_rows, int32_t* rows_out);
+
 /* Checkpoints (no reference counterpart -- the
  * reference's peers keep no state across restarts).  Taken between rounds:
  * the blob holds the whole per-run state of this context (Message-List rows in
