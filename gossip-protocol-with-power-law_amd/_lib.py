@@ -27,6 +27,8 @@ SEEN, FIRST, DIGEST, COVERAGE, FORWARDS, STATE, MISS, DEG_LIVE, ROW_PTR, COL, FR
 JOB_DIGEST, JOB_COVERAGE, JOB_FORWARDS = 13, 14, 15   # after gp_shard_combine
 LOAD_SENT, LOAD_RECV, SEENPOP = 16, 17, 18            # per-peer traffic record (gp_track_load), |Message-List|
 FRESH_SENT, FRESH_RECV = 19, 20                       # per-peer fresh deliveries (gp_track_fresh)
+LINK_FRESH = 21                                       # per-link fresh deliveries (gp_track_link_fresh)
+LINK_BINS = 4097                                      # gp_read_link_hist: counts 0 .. 4096
 # gp_shard_info transports
 XPORT_NONE, XPORT_RCCL, XPORT_HOST = 0, 1, 2
 
@@ -144,7 +146,9 @@ SIGNATURES = {
     "gp_track_fresh": (ctypes.c_int, [_P, _I32]),
     "gp_track_fresh_curve": (ctypes.c_int, [_P, _I32]),
     "gp_read_fresh_curve": (ctypes.c_int, [_P, _P, _I32, _PI32]),
-    "gp_checkpoint_size": (ctypes.c_int, [_P, _PI64]),
+    "gp_track_link_fresh": (ctypes.c_int, [_P, _I32]),
+    "gp_read_link_hist": (ctypes.c_int, [_P, _P, _I32]),
+    "gp_checkpoint_size":(ctypes.c_int, [_P, _PI64]),
     "gp_checkpoint_save": (ctypes.c_int, [_P, _P, _I64]),
     "gp_checkpoint_load": (ctypes.c_int, [_P, _P, _I64]),
 }

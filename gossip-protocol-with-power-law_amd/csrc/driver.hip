@@ -365,8 +365,8 @@ static void fill_expand(Ctx* c, ExpandArgs& a) {
   a.cmk_next = p.cml_write ? c->d_cmk[c->cur ^ 1] : nullptr;
   a.cml_next = p.cml_write ? c->d_cml[c->cur ^ 1] : nullptr;
   // (the push reads the senders' exact rows where some other output keeps them;
-  // rows kept for gp_track_fresh or gp_track_fresh_curve alone leave its source, and so every work
-  // counter of the run, the untracked run's)
+  // rows kept for gp_track_fresh, gp_track_fresh_curve or gp_track_link_fresh alone leave its source, and
+  // so every work counter of the run, the untracked run's)
   const bool frx_src = c->cfg.track_msg_forwards != 0 || c->local || c->curve_want;
   a.frx = c->d_frx[0] && frx_src ? c->d_frx[c->cur] : nullptr;
   a.frx_next = c->d_frx[0] ? c->d_frx[c->cur ^ 1] : nullptr;
@@ -618,7 +618,8 @@ static int round_launch(Ctx* c) {
   GP_HIP(hipEventRecord(c->ev[2], s));
   GP_TRY(curve_count_round(c));   // (nothing is launched unless gp_track_curve is on)
   GP_TRY(fresh_count_round(c));   // (... gp_track_fresh)
-  return fresh_curve_count_round(c);   // (... gp_track_fresh_curve; all after expand_ms ends: round_ms carries them)
+  GP_TRY(fresh_curve_count_round(c));   // (... gp_track_fresh_curve)
+  return link_count_round(c);   // (... gp_track_link_fresh; all after expand_ms ends: round_ms carries them)
 }
 
 // X_r over RCCL.  One rank: the counters' all-reduce is the whole exchange.
@@ -996,6 +997,8 @@ int gp_read(gp_ctx* c, int32_t what, void* host, int64_t bytes) {
     case GP_FRESH_SENT:
     case GP_FRESH_RECV:   // per-peer fresh deliveries (fresh.hip)
       return fresh_read(c, what, host, bytes);
+    case GP_LINK_FRESH:   // per-link fresh deliveries (link.hip)
+      return link_read(c, host, bytes);
     case GP_SEENPOP:
       if (!run) return set_error(GP_ESTATE, "no run state");
       GP_TRY(need(nl * 4));

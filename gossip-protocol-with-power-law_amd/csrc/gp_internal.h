@@ -178,8 +178,18 @@ struct Ctx {
   size_t fresh_curve_words = 0;           // u64 d_fresh_curve holds
   bool fresh_curve_want = false, fresh_curve_alloc = false, fresh_curve_on = false, fresh_curve_valid = false;
   int fresh_curve_grid = 0;               // GP_FRESH_CURVE_GRID at gp_create: cap of k_fresh_curve's grid (0: none)
+  // per-link fresh deliveries (link.hip): the same news per arc
+  // of the in-CSR, the matrix d_fresh_sent / d_fresh_recv are the column / row
+  // sums of.  u16 per arc: over a run arc u -> v counts a message at most once
+  // (v receives it for the first time once), so link_fresh[j] <= m <= 4096 --
+  // and a path with every message injected at one end attains it.  The four
+  // flags are the fresh deliveries'
+  uint16_t* d_link = nullptr;             // [nnz] in-CSR arc order
+  u64* d_link_hist = nullptr;             // [4097] gp_read_link_hist's device result
+  size_t link_arcs = 0;                   // arcs d_link holds
+  bool link_want = false, link_alloc = false, link_on = false, link_valid = false;
   bool holds_frx() const {
-    return cfg.track_msg_forwards != 0 || local || curve_want || fresh_want || fresh_curve_want;
+    return cfg.track_msg_forwards != 0 || local || curve_want || fresh_want || fresh_curve_want || link_want;
   }
   uint32_t* d_fpop[2] = {nullptr, nullptr};    // [n_alloc]
   int cur = 0;
@@ -424,6 +434,12 @@ void fresh_curve_free(Ctx* c);
 int fresh_curve_count_round(Ctx* c);           // after E_r: row r + 1, the deliverers of round r's first receipts
 void fresh_curve_restored(Ctx* c, int32_t round);   // gp_checkpoint_load: a run past round 0 lost its record
 int fresh_curve_env_grid();                    // GP_FRESH_CURVE_GRID in the environment (0: unset)
+// link.hip
+int link_reset(Ctx* c);                        // gp_reset: gp_track_link_fresh takes effect; the record (or none), cleared
+void link_free(Ctx* c);
+int link_count_round(Ctx* c);                  // after E_r: round r's first-receipt deliveries per arc of the in-CSR
+void link_restored(Ctx* c, int32_t round);     // gp_checkpoint_load: a run past round 0 lost its record
+int link_read(Ctx* c, void* host, int64_t bytes);   // GP_LINK_FRESH
 // driver.hip: k_mkbits (and k_mksum) over fpop[cur], ahead of launch_expand
 int launch_activity_bits(Ctx* c, bool summary);
 // driver.hip: cnt[m] += the rows' bit m over rows [0, count) with guard[i] != 0 (the per-bit k_bitsum)

@@ -251,6 +251,7 @@ static void free_state(Ctx* c) {
   load_free(c);
   fresh_free(c);
   fresh_curve_free(c);
+  link_free(c);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_abits); dfree(&c->d_dbits); dfree(&c->d_lm); dfree(&c->d_lmw[0]); dfree(&c->d_lmw[1]); dfree(&c->d_sbits); dfree(&c->d_amask); dfree(&c->d_cml[0]); dfree(&c->d_cml[1]); dfree(&c->d_cmk[0]); dfree(&c->d_cmk[1]); dfree(&c->d_done_at);
@@ -339,11 +340,12 @@ static int alloc_state(Ctx* c) {
   // Message-Lists) and for the boundary exchange of a vertex
   // partition, which sends owned vertices' new bits: the owned rows only (a
   // ghost's slot row is its frontier); the spread curve counts them too, and
-  // the fresh-delivery passes (fresh.hip, fresh_curve.hip) intersect them
-  c->frx_rows = c->local ? c->nloc()
-                         : (c->cfg.track_msg_forwards || c->curve_want || c->fresh_want || c->fresh_curve_want ? c->n_alloc : 0);
+  // the fresh-delivery passes (fresh.hip, fresh_curve.hip, link.hip) intersect them
+  const bool frx_record = c->cfg.track_msg_forwards || c->curve_want || c->fresh_want || c->fresh_curve_want || c->link_want;
+  c->frx_rows = c->local ? c->nloc() : (frx_record ? c->n_alloc : 0);
   c->fresh_alloc = c->fresh_want;
   c->fresh_curve_alloc = c->fresh_curve_want;
+  c->link_alloc = c->link_want;
   dfree(&c->d_slot[2]);   // (re)allocated at the first parking, for this W
   c->carry = RoundCarry{};   // (new buffers carry nothing over; parking may be tried again)
   // S[0] | S[1] | accumulator rows of the owned receivers, one allocation
@@ -607,6 +609,7 @@ void gp_destroy(gp_ctx* c) {
   load_free(c);
   fresh_free(c);
   fresh_curve_free(c);
+  link_free(c);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_stats);
@@ -874,9 +877,10 @@ int gp_spread_keys(gp_ctx* c, int32_t hops, int32_t m, const int32_t* origin, ui
 int gp_reset(gp_ctx* c) {
   if (!c) return set_error(GP_EINVAL, "null ctx");
   GP_HIP(hipSetDevice(c->device));
-  // (gp_track_curve, gp_track_fresh and gp_track_fresh_curve take effect here: frontier rows, the count buffer)
+  // (gp_track_curve, gp_track_fresh, gp_track_fresh_curve and gp_track_link_fresh take effect here: frontier
+  // rows, the count buffer)
   if (!state_ready(c) || c->curve_alloc != c->curve_want || c->fresh_alloc != c->fresh_want ||
-      c->fresh_curve_alloc != c->fresh_curve_want)
+      c->fresh_curve_alloc != c->fresh_curve_want || c->link_alloc != c->link_want)
     GP_TRY(alloc_state(c));
   if (!c->done_at_valid) {
     GP_TRY(compute_done_at(c, c->n_groups));
@@ -926,6 +930,7 @@ int gp_reset(gp_ctx* c) {
   GP_TRY(load_reset(c));   // (gp_track_load takes effect here)
   GP_TRY(fresh_reset(c));  // (and gp_track_fresh)
   GP_TRY(fresh_curve_reset(c));   // (and gp_track_fresh_curve)
+  GP_TRY(link_reset(c));          // (and gp_track_link_fresh)
   GP_HIP(hipStreamSynchronize(s));
   return 0;
 }

@@ -446,6 +446,26 @@ class GossipEngine:
         check(self._lib.gp_read_fresh_curve(self._ctx, _ptr(buf), buf.shape[0], ctypes.byref(rows)))
         return buf[:rows.value].copy()
 
+    # -- per-link fresh deliveries (csrc/link.hip; helpers in links.py) ------
+    def track_link_fresh(self, on=True):
+        """gp_track_link_fresh: keep, per arc of the in-CSR, the first receipts
+        it delivered from the next reset() on."""
+        check(self._lib.gp_track_link_fresh(self._ctx, 1 if on else 0))
+
+    def link_fresh(self):
+        """u16 [nnz]: link_fresh[j] = the messages arc j of graph() (sender
+        col[j], receiver the row of j) delivered since reset() to a receiver
+        that did not hold them; its row sums are fresh_recv(), its sums by
+        col are fresh_sent()."""
+        return self._read(_lib.LINK_FRESH, np.empty(self.info()[1], dtype=np.uint16))
+
+    def link_hist(self):
+        """u64 [4097]: link_hist[c] = arcs with link_fresh() == c, computed on
+        the device (links.hist is its numpy twin)."""
+        buf = np.zeros(_lib.LINK_BINS, dtype=np.uint64)
+        check(self._lib.gp_read_link_hist(self._ctx, _ptr(buf), buf.size))
+        return buf
+
     def _nv(self):   # per-vertex reads: the owned slice of a partitioned context
         return self.nloc() if self.nranks > 1 else self.n
 

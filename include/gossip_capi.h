@@ -194,7 +194,9 @@ typedef enum gp_what {
                          (readable without tracking; exact for aliased vertices)   */
   /* per-peer fresh deliveries (gp_track_fresh below) */
   GP_FRESH_SENT = 19, /* u64 [n]  peer u's sends that delivered a first receipt      */
-  GP_FRESH_RECV = 20  /* u64 [n]  arrivals at peer v of a message it did not hold    */
+  GP_FRESH_RECV = 20, /* u64 [n]  arrivals at peer v of a message it did not hold    */
+  /* per-link fresh deliveries (gp_track_link_fresh below) */
+  GP_LINK_FRESH = 21  /* u16 [nnz]  first receipts arc j of the in-CSR delivered     */
 } gp_what;
 
 int gp_abi_version(void);
@@ -456,6 +458,57 @@ int gp_track_fresh(gp_ctx* ctx, int32_t on);
  * next gp_reset. */
 int gp_track_fresh_curve(gp_ctx* ctx, int32_t on);
 int gp_read_fresh_curve(gp_ctx* ctx, uint64_t* host, int32_t cap_rows, int32_t* rows_out);
+
+/* Per-link fresh deliveries: the fresh deliveries per
+ * overlay link -- the arrival lines of a gossip log (Peer.py:206, Peer.py:286)
+ * that were news, grouped by the connection they came over.  For arc j of the
+ * in-CSR as loaded or built (GP_ROW_PTR / GP_COL), row_ptr[v] <= j <
+ * row_ptr[v + 1] and u = col[j], so sender u and receiver v, over the rounds
+ * run since gp_reset:
+ *   GP_LINK_FRESH  link_fresh[j] = sum_r |frontier_r(u) & new_r(v)|
+ * Several in-neighbours delivering one message in the same round all count,
+ * with no tie-break; an injection has no deliverer; a down receiver has no
+ * new_r, a crashed sender's frontier is dropped, a removed peer is down.  It is
+ * a pure function of the first-receipt matrix: arc u -> v counts message m iff
+ * first[u][m] != 255, first[v][m] = first[u][m] + 1 and u is up in round
+ * first[u][m].  So, all exactly,
+ *   the sum over the arcs of row v is GP_FRESH_RECV[v];
+ *   the sum over the arcs with col[j] = u is GP_FRESH_SENT[u];
+ *   the whole array sums to sum GP_FRESH_RECV = the sum of the fresh-delivery curve.
+ * link_fresh[j] <= m <= 4096, because v first receives each message once: the
+ * record is u16 per arc.  The bound is attained (a path with every message
+ * injected at one end: 4096 on the arcs pointing away from it, 0 on the arcs
+ * pointing back).  An undirected link is two arcs, u -> v and v -> u, counted
+ * separately (links.undirected of the Python package folds them).  Readable
+ * between rounds.  A context that runs a block of a message table
+ * (msg_word_base) holds the counts of its own messages: the shards' arrays add
+ * up element by element to the whole run's (the host adds them;
+ * gp_shard_combine does not).
+ *
+ * gp_read_link_hist computes, on the device and from the current record,
+ * link_hist[c] = the number of arcs with link_fresh = c for c = 0 .. 4096:
+ * link_hist[0] is the idle arcs, and the fewest arcs that carry a given share
+ * of the news follow from the histogram alone, without reading the array.
+ * `bins` must be 4097 (else GP_EINVAL, nothing written).  The histograms of a
+ * job's shards do not add up to the whole run's.
+ *
+ * gp_track_link_fresh(on) takes effect at the next gp_reset, which makes the
+ * exact frontier rows exist (shared with track_msg_forwards and the other
+ * records when several are on) and allocates (and clears) the u16[nnz]; off,
+ * nothing is allocated or launched, and turning it off frees the array at the
+ * next gp_reset.  Loading another overlay re-sizes it.  Every round then adds
+ * one pass after the expansion (round_ms carries it; expand_ms and kernel_ms
+ * keep their meaning).  Tracking changes no other output and no counter, the
+ * work counters included, and makes neither GP_FRONTIER nor GP_FORWARDS
+ * readable.
+ *
+ * Reads (gp_read GP_LINK_FRESH and gp_read_link_hist): GP_ENOTRACK before
+ * tracking took effect, and on a vertex-partitioned context (nranks > 1: not
+ * supported); GP_ESTATE for a run restored from a checkpoint past round 0 (the
+ * blob does not hold the record), until the next gp_reset; GP_EINVAL on a
+ * byte-count mismatch (expected 2 * nnz). */
+int gp_track_link_fresh(gp_ctx* ctx, int32_t on);
+int gp_read_link_hist(gp_ctx* ctx, uint64_t* hist, int32_t bins);
 
 /* Checkpoints (no reference counterpart -- the
  * reference's peers keep no state across restarts).  Taken between rounds:
