@@ -29,6 +29,8 @@ LOAD_SENT, LOAD_RECV, SEENPOP = 16, 17, 18            # per-peer traffic record 
 FRESH_SENT, FRESH_RECV = 19, 20                       # per-peer fresh deliveries (gp_track_fresh)
 LINK_FRESH = 21                                       # per-link fresh deliveries (gp_track_link_fresh)
 LINK_BINS = 4097                                      # gp_read_link_hist: counts 0 .. 4096
+DELAY_SUM, DELAY_MAX = 22, 23                         # per-peer receipt delays (gp_track_delay)
+DELAY_BINS, DELAY_COLS = 32, 5                        # gp_read_delay_bins: degree bins x columns
 # gp_shard_info transports
 XPORT_NONE, XPORT_RCCL, XPORT_HOST = 0, 1, 2
 
@@ -148,6 +150,8 @@ SIGNATURES = {
     "gp_read_fresh_curve": (ctypes.c_int, [_P, _P, _I32, _PI32]),
     "gp_track_link_fresh": (ctypes.c_int, [_P, _I32]),
     "gp_read_link_hist": (ctypes.c_int, [_P, _P, _I32]),
+    "gp_track_delay": (ctypes.c_int, [_P, _I32]),
+    "gp_read_delay_bins": (ctypes.c_int, [_P, _P, _I32]),
     "gp_checkpoint_size":(ctypes.c_int, [_P, _PI64]),
     "gp_checkpoint_save": (ctypes.c_int, [_P, _P, _I64]),
     "gp_checkpoint_load": (ctypes.c_int, [_P, _P, _I64]),

@@ -619,7 +619,8 @@ static int round_launch(Ctx* c) {
   GP_TRY(curve_count_round(c));   // (nothing is launched unless gp_track_curve is on)
   GP_TRY(fresh_count_round(c));   // (... gp_track_fresh)
   GP_TRY(fresh_curve_count_round(c));   // (... gp_track_fresh_curve)
-  return link_count_round(c);   // (... gp_track_link_fresh; all after expand_ms ends: round_ms carries them)
+  GP_TRY(link_count_round(c));   // (... gp_track_link_fresh)
+  return delay_count_round(c);   // (... gp_track_delay; all after expand_ms ends: round_ms carries them)
 }
 
 // X_r over RCCL.  One rank: the counters' all-reduce is the whole exchange.
@@ -999,6 +1000,9 @@ int gp_read(gp_ctx* c, int32_t what, void* host, int64_t bytes) {
       return fresh_read(c, what, host, bytes);
     case GP_LINK_FRESH:   // per-link fresh deliveries (link.hip)
       return link_read(c, host, bytes);
+    case GP_DELAY_SUM:
+    case GP_DELAY_MAX:   // per-peer receipt delays (delay.hip)
+      return delay_read(c, what, host, bytes);
     case GP_SEENPOP:
       if (!run) return set_error(GP_ESTATE, "no run state");
       GP_TRY(need(nl * 4));

@@ -188,8 +188,27 @@ struct Ctx {
   u64* d_link_hist = nullptr;             // [4097] gp_read_link_hist's device result
   size_t link_arcs = 0;                   // arcs d_link holds
   bool link_want = false, link_alloc = false, link_on = false, link_valid = false;
+  // per-peer receipt delays (delay.hip): over the owned
+  // vertices, the sum and the maximum of first[v][k] - inject_round[k] over the
+  // messages v holds.  delay_want is what gp_track_delay asked for, delay_alloc
+  // whether alloc_state sized the frontier rows for it (a table whose messages
+  // all start in one round needs none: delay_uniform), delay_on what the run
+  // since the last gp_reset keeps, delay_valid falls when a checkpoint restores
+  // the run past round 0.  Partitioned contexts keep it for their owned slice
+  uint32_t* d_delay_sum = nullptr;        // [nloc]
+  uint8_t* d_delay_max = nullptr;         // [nloc]
+  u64* d_delay_planes = nullptr;          // [8][W] inject-round planes of the context's table (delay_planes.h)
+  u64* d_delay_bins = nullptr;            // [32][5] gp_read_delay_bins' device result
+  size_t delay_rows = 0;                  // vertices the two arrays hold
+  std::vector<uint8_t> h_inj_round;       // [m] inject round of every message of the context's table
+  int32_t delay_uniform = -1;             // the table's one inject round (-1: they differ)
+  bool delay_want = false, delay_alloc = false, delay_on = false, delay_valid = false;
+  bool delay_force_rows = false;          // GP_DELAY_ROWS=1 at gp_create: the row pass for a one-round table too
+  bool delay_by_rows() const { return delay_uniform < 0 || delay_force_rows; }
+  bool delay_needs_rows() const { return delay_want && delay_by_rows(); }
   bool holds_frx() const {
-    return cfg.track_msg_forwards != 0 || local || curve_want || fresh_want || fresh_curve_want || link_want;
+    return cfg.track_msg_forwards != 0 || local || curve_want || fresh_want || fresh_curve_want || link_want ||
+           delay_needs_rows();
   }
   uint32_t* d_fpop[2] = {nullptr, nullptr};    // [n_alloc]
   int cur = 0;
@@ -440,6 +459,13 @@ void link_free(Ctx* c);
 int link_count_round(Ctx* c);                  // after E_r: round r's first-receipt deliveries per arc of the in-CSR
 void link_restored(Ctx* c, int32_t round);     // gp_checkpoint_load: a run past round 0 lost its record
 int link_read(Ctx* c, void* host, int64_t bytes);   // GP_LINK_FRESH
+// delay.hip
+int delay_reset(Ctx* c);                       // gp_reset: gp_track_delay takes effect; the record (or none), cleared
+void delay_free(Ctx* c);
+int delay_count_round(Ctx* c);                 // after E_r: the delays of round r's first receipts, per receiver
+void delay_restored(Ctx* c, int32_t round);    // gp_checkpoint_load: a run past round 0 lost its record
+bool delay_env_rows();                         // GP_DELAY_ROWS=1 in the environment
+int delay_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_DELAY_SUM / GP_DELAY_MAX
 // driver.hip: k_mkbits (and k_mksum) over fpop[cur], ahead of launch_expand
 int launch_activity_bits(Ctx* c, bool summary);
 // driver.hip: cnt[m] += the rows' bit m over rows [0, count) with guard[i] != 0 (the per-bit k_bitsum)

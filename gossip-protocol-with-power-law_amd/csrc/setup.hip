@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "block_order.h"
+#include "delay_planes.h"
 #include "gp_device.h"
 #include "line_cands.h"
 #include "xplan.h"
@@ -252,6 +253,7 @@ static void free_state(Ctx* c) {
   fresh_free(c);
   fresh_curve_free(c);
   link_free(c);
+  delay_free(c);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_abits); dfree(&c->d_dbits); dfree(&c->d_lm); dfree(&c->d_lmw[0]); dfree(&c->d_lmw[1]); dfree(&c->d_sbits); dfree(&c->d_amask); dfree(&c->d_cml[0]); dfree(&c->d_cml[1]); dfree(&c->d_cmk[0]); dfree(&c->d_cmk[1]); dfree(&c->d_done_at);
@@ -341,11 +343,14 @@ static int alloc_state(Ctx* c) {
   // partition, which sends owned vertices' new bits: the owned rows only (a
   // ghost's slot row is its frontier); the spread curve counts them too, and
   // the fresh-delivery passes (fresh.hip, fresh_curve.hip, link.hip) intersect them
-  const bool frx_record = c->cfg.track_msg_forwards || c->curve_want || c->fresh_want || c->fresh_curve_want || c->link_want;
+  // (the receipt delays read the receivers' own new rows, delay.hip -- unless every message starts in one round)
+  const bool frx_record = c->cfg.track_msg_forwards || c->curve_want || c->fresh_want || c->fresh_curve_want ||
+                          c->link_want || c->delay_needs_rows();
   c->frx_rows = c->local ? c->nloc() : (frx_record ? c->n_alloc : 0);
   c->fresh_alloc = c->fresh_want;
   c->fresh_curve_alloc = c->fresh_curve_want;
   c->link_alloc = c->link_want;
+  c->delay_alloc = c->delay_needs_rows();
   dfree(&c->d_slot[2]);   // (re)allocated at the first parking, for this W
   c->carry = RoundCarry{};   // (new buffers carry nothing over; parking may be tried again)
   // S[0] | S[1] | accumulator rows of the owned receivers, one allocation
@@ -558,6 +563,7 @@ int gp_create(int device, gp_ctx** out) {
   c->curve_yard = curve_env_yardstick();
   c->load_force = load_env_eager();   // (a test lever: the per-round traffic pass from round 0, load.hip)
   c->fresh_gather = fresh_env_gather();   // (the A/B lever of the fresh-delivery pass, fresh.hip)
+  c->delay_force_rows = delay_env_rows();   // (the A/B lever of the receipt-delay pass, delay.hip)
   c->fresh_curve_grid = fresh_curve_env_grid();   // (a test lever, as GP_CURVE_GRID: few blocks fill k_fresh_curve's planes)
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->cu_count = prop.multiProcessorCount;
@@ -610,6 +616,7 @@ void gp_destroy(gp_ctx* c) {
   fresh_free(c);
   fresh_curve_free(c);
   link_free(c);
+  delay_free(c);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_stats);
@@ -810,6 +817,10 @@ int gp_set_messages(gp_ctx* c, int32_t m, const int32_t* origin, const int32_t* 
   }
   c->m = m;
   c->last_inject_round = last;
+  // (the table's inject rounds, for the receipt delays: delay.hip builds its planes from them at gp_reset)
+  c->h_inj_round.resize((size_t)m);
+  for (int32_t k = 0; k < m; ++k) c->h_inj_round[(size_t)k] = (uint8_t)(inject_round ? inject_round[k] : 0);
+  c->delay_uniform = delay_uniform_round(c->h_inj_round.data(), m);
   const bool realloc = words != c->words || c->n_alloc != nv_before;
   c->words = words;
   GP_TRY(dalloc(&c->d_inj_origin, g_origin.size()));
@@ -880,7 +891,8 @@ int gp_reset(gp_ctx* c) {
   // (gp_track_curve, gp_track_fresh, gp_track_fresh_curve and gp_track_link_fresh take effect here: frontier
   // rows, the count buffer)
   if (!state_ready(c) || c->curve_alloc != c->curve_want || c->fresh_alloc != c->fresh_want ||
-      c->fresh_curve_alloc != c->fresh_curve_want || c->link_alloc != c->link_want)
+      c->fresh_curve_alloc != c->fresh_curve_want || c->link_alloc != c->link_want ||
+      c->delay_alloc != c->delay_needs_rows())   // (gp_track_delay: rows only for a table of several inject rounds)
     GP_TRY(alloc_state(c));
   if (!c->done_at_valid) {
     GP_TRY(compute_done_at(c, c->n_groups));
@@ -931,6 +943,7 @@ int gp_reset(gp_ctx* c) {
   GP_TRY(fresh_reset(c));  // (and gp_track_fresh)
   GP_TRY(fresh_curve_reset(c));   // (and gp_track_fresh_curve)
   GP_TRY(link_reset(c));          // (and gp_track_link_fresh)
+  GP_TRY(delay_reset(c));         // (and gp_track_delay)
   GP_HIP(hipStreamSynchronize(s));
   return 0;
 }

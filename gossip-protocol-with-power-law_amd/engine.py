@@ -466,6 +466,30 @@ class GossipEngine:
         check(self._lib.gp_read_link_hist(self._ctx, _ptr(buf), buf.size))
         return buf
 
+    # -- per-peer receipt delays (csrc/delay.hip; helpers in latency.py) -----
+    def track_delay(self, on=True):
+        """gp_track_delay: keep, per owned peer, the sum and the maximum of its
+        receipt delays (receipt round - inject round) from the next reset() on."""
+        check(self._lib.gp_track_delay(self._ctx, 1 if on else 0))
+
+    def delay_sum(self):
+        """u32 per owned vertex: the sum of v's receipt delays since reset(),
+        over the seenpop()[v] messages it holds (latency.mean_delay divides)."""
+        return self._read(_lib.DELAY_SUM, np.empty(self.nloc(), dtype=np.uint32))
+
+    def delay_max(self):
+        """u8 per owned vertex: v's largest receipt delay since reset() (0 for
+        a peer that holds nothing, or only what was injected at it)."""
+        return self._read(_lib.DELAY_MAX, np.empty(self.nloc(), dtype=np.uint8))
+
+    def delay_bins(self):
+        """u64 [32][5]: the record by degree bin, computed on the device
+        (latency.bins is its numpy twin, latency.by_degree reads it): peers,
+        peers reached, receipts, sum of delay_sum, max of delay_max."""
+        buf = np.zeros((_lib.DELAY_BINS, _lib.DELAY_COLS), dtype=np.uint64)
+        check(self._lib.gp_read_delay_bins(self._ctx, _ptr(buf), buf.shape[0]))
+        return buf
+
     def _nv(self):   # per-vertex reads: the owned slice of a partitioned context
         return self.nloc() if self.nranks > 1 else self.n
 

@@ -196,7 +196,10 @@ typedef enum gp_what {
   GP_FRESH_SENT = 19, /* u64 [n]  peer u's sends that delivered a first receipt      */
   GP_FRESH_RECV = 20, /* u64 [n]  arrivals at peer v of a message it did not hold    */
   /* per-link fresh deliveries (gp_track_link_fresh below) */
-  GP_LINK_FRESH = 21  /* u16 [nnz]  first receipts arc j of the in-CSR delivered     */
+  GP_LINK_FRESH = 21, /* u16 [nnz]  first receipts arc j of the in-CSR delivered     */
+  /* per-peer receipt delays (gp_track_delay below) */
+  GP_DELAY_SUM = 22,  /* u32 [vend-vbegin]  sum of v's receipt delays, in rounds     */
+  GP_DELAY_MAX = 23   /* u8  [vend-vbegin]  v's largest receipt delay (0: none)      */
 } gp_what;
 
 int gp_abi_version(void);
@@ -509,6 +512,66 @@ int gp_read_fresh_curve(gp_ctx* ctx, uint64_t* host, int32_t cap_rows, int32_t* 
  * byte-count mismatch (expected 2 * nnz). */
 int gp_track_link_fresh(gp_ctx* ctx, int32_t on);
 int gp_read_link_hist(gp_ctx* ctx, uint64_t* hist, int32_t bins);
+
+/* Per-peer receipt delays: how late every peer hears
+ * the news -- the arrival lines of a gossip log carry their time (Peer.py:206,
+ * Peer.py:286); grouped by the receiving peer they say how long after a
+ * message was generated that peer heard it.  For an owned vertex v, over the
+ * messages k of the context's table:
+ *   GP_DELAY_SUM  delay_sum[v] = sum_{k : first[v][k] != 255} (first[v][k] - inject_round[k])
+ *   GP_DELAY_MAX  delay_max[v] = max_{k : first[v][k] != 255} (first[v][k] - inject_round[k]),
+ *                 0 if v holds nothing
+ * GP_SEENPOP[v] is the number of terms: the mean delay is delay_sum / seenpop,
+ * and a peer with seenpop = 0 was never reached (delay_max = 0 alone does not
+ * say so: an origin that only holds its own messages has it too).  An injection
+ * at an up origin is a receipt with delay 0.  A receipt of round r's expansion
+ * has receipt round r + 1 and delay r + 1 - inject_round[k] >= 1; it counts when
+ * it happens, so a receiver that crashes in round r + 1 still received.  In the
+ * round-synchronous model a delay is the receiver's hop distance from the
+ * origin on the live overlay: the mean is a sampled closeness, the maximum a
+ * sampled eccentricity.  Both arrays are pure functions of the first-receipt
+ * matrix and the message table.  delay_max <= 254 (inject_round <= 253, rounds
+ * stop at 253) and delay_sum <= 4096 * 254 < 2^21.  Over a single-rank run,
+ *   sum_v delay_sum[v] = sum_R sum_k (R - inject_round[k]) * curve[R][k], exactly.
+ * The arrays hold totals since gp_reset and are readable between rounds: after
+ * R rounds, the receipts with first <= R.  A context that runs a block of a
+ * message table (msg_word_base) holds its own messages' terms: the shards'
+ * delay_sum arrays add up and delay_max is their element-wise maximum (the
+ * host combines them; gp_shard_combine does not).  A vertex-partitioned
+ * context keeps the record for its owned vertices, read as [vend - vbegin]
+ * like GP_SEENPOP.
+ *
+ * gp_read_delay_bins computes, on the device and from the current record, the
+ * delays by degree: a u64 [GP_DELAY_BINS][GP_DELAY_COLS] table whose row b
+ * holds the owned vertices with bin(deg) = b, where deg is the vertex's
+ * in-list length in the context's CSR and bin(deg) = 0 for deg <= 1, else
+ * floor(log2(deg)).  Columns: peers; peers reached (seenpop > 0); receipts
+ * (sum seenpop); sum delay_sum; max delay_max.  Over shards or partition
+ * ranks, columns 0-3 add where the vertex sets are disjoint (over shards of one
+ * vertex set columns 2-3 add), and column 4 takes the maximum.  `bins` must be
+ * GP_DELAY_BINS (else GP_EINVAL, nothing written).
+ *
+ * gp_track_delay(on) takes effect at the next gp_reset, which allocates (and
+ * clears) 5 bytes per owned vertex; off, nothing is allocated or launched, and
+ * turning it off frees the arrays at the next gp_reset.  Every round then adds
+ * one pass after the expansion (round_ms carries it; expand_ms and kernel_ms
+ * keep their meaning): over the receivers' own new rows -- the exact frontier
+ * rows, which the reset makes exist -- or, when every message of the table has
+ * the same inject round, over the per-vertex counts alone: such a table keeps
+ * no frontier rows for this record (GP_DELAY_ROWS=1 in the environment at
+ * gp_create takes the row pass, and keeps the rows, for such a table too: a
+ * test and measurement lever, same arrays).  Tracking changes no other output and no
+ * counter, and makes neither GP_FRONTIER nor GP_FORWARDS readable.
+ *
+ * Reads (gp_read GP_DELAY_SUM / GP_DELAY_MAX and gp_read_delay_bins):
+ * GP_ENOTRACK before tracking took effect; GP_ESTATE for a run restored from a
+ * checkpoint past round 0 (the blob does not hold the record), until the next
+ * gp_reset; GP_EINVAL on a byte-count mismatch (expected 4 or 1 per owned
+ * vertex), a bin-count mismatch or a null argument. */
+#define GP_DELAY_BINS 32
+#define GP_DELAY_COLS 5
+int gp_track_delay(gp_ctx* ctx, int32_t on);
+int gp_read_delay_bins(gp_ctx* ctx, uint64_t* out, int32_t bins);
 
 /* Checkpoints (no reference counterpart -- the
  * reference's peers keep no state across restarts).  Taken between rounds:
