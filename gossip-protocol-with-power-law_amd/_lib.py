@@ -31,6 +31,9 @@ LINK_FRESH = 21                                       # per-link fresh deliverie
 LINK_BINS = 4097                                      # gp_read_link_hist: counts 0 .. 4096
 DELAY_SUM, DELAY_MAX = 22, 23                         # per-peer receipt delays (gp_track_delay)
 DELAY_BINS, DELAY_COLS = 32, 5                        # gp_read_delay_bins: degree bins x columns
+SOLE_SENT, SOLE_RECV = 24, 25                         # delivery multiplicity (gp_track_mult)
+MULT_BINS = 17                                        # gp_read_mult_hist: 0 .. 15 deliverers, 16 or more
+SOLE_BINS, SOLE_COLS = 32, 4                          # gp_read_sole_bins: degree bins x columns
 # gp_shard_info transports
 XPORT_NONE, XPORT_RCCL, XPORT_HOST = 0, 1, 2
 
@@ -152,6 +155,9 @@ SIGNATURES = {
     "gp_read_link_hist": (ctypes.c_int, [_P, _P, _I32]),
     "gp_track_delay": (ctypes.c_int, [_P, _I32]),
     "gp_read_delay_bins": (ctypes.c_int, [_P, _P, _I32]),
+    "gp_track_mult": (ctypes.c_int, [_P, _I32]),
+    "gp_read_mult_hist": (ctypes.c_int, [_P, _P, _I32]),
+    "gp_read_sole_bins": (ctypes.c_int, [_P, _P, _I32]),
     "gp_checkpoint_size":(ctypes.c_int, [_P, _PI64]),
     "gp_checkpoint_save": (ctypes.c_int, [_P, _P, _I64]),
     "gp_checkpoint_load": (ctypes.c_int, [_P, _P, _I64]),

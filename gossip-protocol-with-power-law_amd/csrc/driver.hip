@@ -618,6 +618,7 @@ static int round_launch(Ctx* c) {
   GP_HIP(hipEventRecord(c->ev[2], s));
   GP_TRY(curve_count_round(c));   // (nothing is launched unless gp_track_curve is on)
   GP_TRY(fresh_count_round(c));   // (... gp_track_fresh)
+  GP_TRY(mult_count_round(c));    // (... gp_track_mult)
   GP_TRY(fresh_curve_count_round(c));   // (... gp_track_fresh_curve)
   GP_TRY(link_count_round(c));   // (... gp_track_link_fresh)
   return delay_count_round(c);   // (... gp_track_delay; all after expand_ms ends: round_ms carries them)
@@ -1003,6 +1004,9 @@ int gp_read(gp_ctx* c, int32_t what, void* host, int64_t bytes) {
     case GP_DELAY_SUM:
     case GP_DELAY_MAX:   // per-peer receipt delays (delay.hip)
       return delay_read(c, what, host, bytes);
+    case GP_SOLE_SENT:
+    case GP_SOLE_RECV:   // delivery multiplicity (mult.hip)
+      return mult_read(c, what, host, bytes);
     case GP_SEENPOP:
       if (!run) return set_error(GP_ESTATE, "no run state");
       GP_TRY(need(nl * 4));

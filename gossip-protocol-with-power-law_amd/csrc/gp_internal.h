@@ -206,9 +206,21 @@ struct Ctx {
   bool delay_force_rows = false;          // GP_DELAY_ROWS=1 at gp_create: the row pass for a one-round table too
   bool delay_by_rows() const { return delay_uniform < 0 || delay_force_rows; }
   bool delay_needs_rows() const { return delay_want && delay_by_rows(); }
+  // delivery multiplicity (mult.hip): how many in-neighbours
+  // delivered each first receipt -- the histogram of that number, and per peer
+  // the receipts with one deliverer, as receiver and as that deliverer.  The
+  // four flags are the fresh deliveries' (single-rank contexts only)
+  uint32_t* d_sole_recv = nullptr;        // [n]
+  u64* d_sole_sent = nullptr;             // [n]
+  u64* d_mult_hist = nullptr;             // [256][17] copies of the histogram (bin 0 unused: the injections)
+  u64* d_sole_bins = nullptr;             // [32][4] gp_read_sole_bins' device result
+  u64* d_mult_scratch = nullptr;          // [n_hub_items][5][W] the hub items' counters of one round
+  u64* d_mult_hub_sole = nullptr;         // [n_hubs][W] the hubs' sole masks of one round
+  size_t mult_rows = 0, mult_scratch_words = 0, mult_hub_words = 0;   // what the arrays were sized for
+  bool mult_want = false, mult_alloc = false, mult_on = false, mult_valid = false;
   bool holds_frx() const {
     return cfg.track_msg_forwards != 0 || local || curve_want || fresh_want || fresh_curve_want || link_want ||
-           delay_needs_rows();
+           delay_needs_rows() || mult_want;
   }
   uint32_t* d_fpop[2] = {nullptr, nullptr};    // [n_alloc]
   int cur = 0;
@@ -466,6 +478,12 @@ int delay_count_round(Ctx* c);                 // after E_r: the delays of round
 void delay_restored(Ctx* c, int32_t round);    // gp_checkpoint_load: a run past round 0 lost its record
 bool delay_env_rows();                         // GP_DELAY_ROWS=1 in the environment
 int delay_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_DELAY_SUM / GP_DELAY_MAX
+// mult.hip
+int mult_reset(Ctx* c);                        // gp_reset: gp_track_mult takes effect; the record (or none), cleared
+void mult_free(Ctx* c);
+int mult_count_round(Ctx* c);                  // after E_r: the deliverer counts of round r's first receipts
+void mult_restored(Ctx* c, int32_t round);     // gp_checkpoint_load: a run past round 0 lost its record
+int mult_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_SOLE_SENT / GP_SOLE_RECV
 // driver.hip: k_mkbits (and k_mksum) over fpop[cur], ahead of launch_expand
 int launch_activity_bits(Ctx* c, bool summary);
 // driver.hip: cnt[m] += the rows' bit m over rows [0, count) with guard[i] != 0 (the per-bit k_bitsum)

@@ -254,6 +254,7 @@ static void free_state(Ctx* c) {
   fresh_curve_free(c);
   link_free(c);
   delay_free(c);
+  mult_free(c);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_abits); dfree(&c->d_dbits); dfree(&c->d_lm); dfree(&c->d_lmw[0]); dfree(&c->d_lmw[1]); dfree(&c->d_sbits); dfree(&c->d_amask); dfree(&c->d_cml[0]); dfree(&c->d_cml[1]); dfree(&c->d_cmk[0]); dfree(&c->d_cmk[1]); dfree(&c->d_done_at);
@@ -345,12 +346,13 @@ static int alloc_state(Ctx* c) {
   // the fresh-delivery passes (fresh.hip, fresh_curve.hip, link.hip) intersect them
   // (the receipt delays read the receivers' own new rows, delay.hip -- unless every message starts in one round)
   const bool frx_record = c->cfg.track_msg_forwards || c->curve_want || c->fresh_want || c->fresh_curve_want ||
-                          c->link_want || c->delay_needs_rows();
+                          c->link_want || c->delay_needs_rows() || c->mult_want;   // (and mult.hip)
   c->frx_rows = c->local ? c->nloc() : (frx_record ? c->n_alloc : 0);
   c->fresh_alloc = c->fresh_want;
   c->fresh_curve_alloc = c->fresh_curve_want;
   c->link_alloc = c->link_want;
   c->delay_alloc = c->delay_needs_rows();
+  c->mult_alloc = c->mult_want;
   dfree(&c->d_slot[2]);   // (re)allocated at the first parking, for this W
   c->carry = RoundCarry{};   // (new buffers carry nothing over; parking may be tried again)
   // S[0] | S[1] | accumulator rows of the owned receivers, one allocation
@@ -617,6 +619,7 @@ void gp_destroy(gp_ctx* c) {
   fresh_curve_free(c);
   link_free(c);
   delay_free(c);
+  mult_free(c);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_stats);
@@ -892,7 +895,8 @@ int gp_reset(gp_ctx* c) {
   // rows, the count buffer)
   if (!state_ready(c) || c->curve_alloc != c->curve_want || c->fresh_alloc != c->fresh_want ||
       c->fresh_curve_alloc != c->fresh_curve_want || c->link_alloc != c->link_want ||
-      c->delay_alloc != c->delay_needs_rows())   // (gp_track_delay: rows only for a table of several inject rounds)
+      c->delay_alloc != c->delay_needs_rows() ||   // (gp_track_delay: rows only for a table of several inject rounds)
+      c->mult_alloc != c->mult_want)               // (gp_track_mult)
     GP_TRY(alloc_state(c));
   if (!c->done_at_valid) {
     GP_TRY(compute_done_at(c, c->n_groups));
@@ -944,6 +948,7 @@ int gp_reset(gp_ctx* c) {
   GP_TRY(fresh_curve_reset(c));   // (and gp_track_fresh_curve)
   GP_TRY(link_reset(c));          // (and gp_track_link_fresh)
   GP_TRY(delay_reset(c));         // (and gp_track_delay)
+  GP_TRY(mult_reset(c));          // (and gp_track_mult)
   GP_HIP(hipStreamSynchronize(s));
   return 0;
 }

@@ -490,6 +490,38 @@ class GossipEngine:
         check(self._lib.gp_read_delay_bins(self._ctx, _ptr(buf), buf.shape[0]))
         return buf
 
+    # -- delivery multiplicity (csrc/mult.hip; helpers in fragility.py) -------
+    def track_mult(self, on=True):
+        """gp_track_mult: keep, from the next reset() on, how many in-neighbours
+        delivered each first receipt -- the histogram of that number and the
+        per-peer counts of receipts with a single deliverer."""
+        check(self._lib.gp_track_mult(self._ctx, 1 if on else 0))
+
+    def sole_sent(self):
+        """u64 [n]: the first receipts, over all of u's out-arcs, for which u was
+        the only deliverer since reset()."""
+        return self._read(_lib.SOLE_SENT, np.empty(self.n, dtype=np.uint64))
+
+    def sole_recv(self):
+        """u32 [n]: v's first receipts since reset() that had one deliverer."""
+        return self._read(_lib.SOLE_RECV, np.empty(self.n, dtype=np.uint32))
+
+    def mult_hist(self):
+        """u64 [17]: first receipts by deliverer count -- hist[c] for c = 1 .. 15,
+        16 or more in hist[16], the injections at up origins in hist[0]
+        (fragility.sole_share / at_least read it)."""
+        buf = np.zeros(_lib.MULT_BINS, dtype=np.uint64)
+        check(self._lib.gp_read_mult_hist(self._ctx, _ptr(buf), buf.size))
+        return buf
+
+    def sole_bins(self):
+        """u64 [32][4]: the record by degree bin, computed on the device
+        (fragility.bins is its numpy twin, fragility.by_degree reads it):
+        peers, receipts, sum of sole_recv, sum of sole_sent."""
+        buf = np.zeros((_lib.SOLE_BINS, _lib.SOLE_COLS), dtype=np.uint64)
+        check(self._lib.gp_read_sole_bins(self._ctx, _ptr(buf), buf.shape[0]))
+        return buf
+
     def _nv(self):   # per-vertex reads: the owned slice of a partitioned context
         return self.nloc() if self.nranks > 1 else self.n
 

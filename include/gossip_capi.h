@@ -199,7 +199,10 @@ typedef enum gp_what {
   GP_LINK_FRESH = 21, /* u16 [nnz]  first receipts arc j of the in-CSR delivered     */
   /* per-peer receipt delays (gp_track_delay below) */
   GP_DELAY_SUM = 22,  /* u32 [vend-vbegin]  sum of v's receipt delays, in rounds     */
-  GP_DELAY_MAX = 23   /* u8  [vend-vbegin]  v's largest receipt delay (0: none)      */
+  GP_DELAY_MAX = 23,  /* u8  [vend-vbegin]  v's largest receipt delay (0: none)      */
+  /* delivery multiplicity (gp_track_mult below) */
+  GP_SOLE_SENT = 24,  /* u64 [n]  first receipts peer u alone delivered, over its out-arcs */
+  GP_SOLE_RECV = 25   /* u32 [n]  first receipts of peer v that had one deliverer     */
 } gp_what;
 
 int gp_abi_version(void);
@@ -572,6 +575,66 @@ int gp_read_link_hist(gp_ctx* ctx, uint64_t* hist, int32_t bins);
 #define GP_DELAY_COLS 5
 int gp_track_delay(gp_ctx* ctx, int32_t on);
 int gp_read_delay_bins(gp_ctx* ctx, uint64_t* out, int32_t bins);
+
+/* Delivery multiplicity: how fragile the flood was.
+ * The fresh-delivery records are sums over deliverers; this one keeps the
+ * number of deliverers behind each first receipt -- the arrival lines of one
+ * message at one peer in the round it was news (Peer.py:206, Peer.py:286).  A
+ * receipt with ten deliverers survives nine crashed neighbours; a receipt with
+ * one hangs on a single link and a single peer.  With frontier_r(u) and
+ * new_r(v) as for the fresh deliveries, for k in new_r(v)
+ *   mult_r(v, k) = #{ arcs j of row v of the in-CSR : k in frontier_r(col[j]) }  >= 1
+ * (parallel arcs count separately; no tie-break is involved; an injection at an
+ * up origin is a receipt with no deliverer).  Over the rounds since gp_reset:
+ *   gp_read_mult_hist  u64 [GP_MULT_BINS]: hist[c], c = 1 .. 15, the first
+ *                 receipts with exactly c deliverers; hist[16] those with 16 or
+ *                 more; hist[0] the injections at up origins (taken from the
+ *                 rounds' `injected` counters)
+ *   GP_SOLE_RECV  sole_recv[v]: v's receipts with mult = 1 (<= m <= 4096)
+ *   GP_SOLE_SENT  sole_sent[u]: the receipts, over all of u's out-arcs, for
+ *                 which u was the only deliverer -- the news that would have
+ *                 arrived later or never without u
+ *   gp_read_sole_bins  u64 [GP_SOLE_BINS][GP_SOLE_COLS], computed on the device
+ *                 from the current record: row b holds the vertices with
+ *                 bin(in-list length) = b (gp_read_delay_bins' bins); columns:
+ *                 peers; receipts (sum GP_SEENPOP); sum sole_recv; sum sole_sent
+ * From the first-receipt matrix: for first[v][k] != 255 the deliverers are the
+ * arcs u -> v with first[u][k] != 255, first[v][k] = first[u][k] + 1 and u up
+ * in round first[u][k]; c is their number, and c = 0 iff the receipt is the
+ * injection.  Exactly:
+ *   sum_c hist[c] = sum_k coverage[k] (single rank, after gp_finalize),
+ *   sum_{c >= 1} hist[c] = sum_r stats[r].new_bits,
+ *   hist[1] = sum sole_recv = sum sole_sent,
+ *   sole_recv[v] <= GP_SEENPOP[v] - (messages injected at v),
+ * and with gp_track_fresh as well sole_recv <= fresh_recv, sole_sent <=
+ * fresh_sent element by element and sum_{c <= 15} c * hist[c] + 16 * hist[16]
+ * <= sum fresh_recv.  The arrays hold totals since gp_reset and are readable
+ * between rounds: after R rounds, the receipts with first <= R.  A context
+ * that runs a block of a message table (msg_word_base) holds its own messages'
+ * receipts: the shards' three arrays, the histogram included, add up element
+ * by element (the host adds them; gp_shard_combine does not).
+ *
+ * gp_track_mult(on) takes effect at the next gp_reset, which makes the exact
+ * frontier rows exist and allocates (and clears) 12 bytes per vertex plus the
+ * hubs' scratch (5 rows per hub item and one per hub, 8 * W bytes each); off,
+ * nothing is allocated or launched, and turning it off frees everything at the
+ * next gp_reset.  Every round then adds one pass after the expansion (round_ms
+ * carries it; expand_ms and kernel_ms keep their meaning).  Tracking changes
+ * no other output and no counter, and makes neither GP_FRONTIER nor
+ * GP_FORWARDS readable.
+ *
+ * Reads (gp_read GP_SOLE_SENT / GP_SOLE_RECV, gp_read_mult_hist,
+ * gp_read_sole_bins): GP_ENOTRACK before tracking took effect, and on a
+ * vertex-partitioned context (not supported); GP_ESTATE for a run restored
+ * from a checkpoint past round 0 (the blob does not hold the record), until
+ * the next gp_reset; GP_EINVAL on a byte-count mismatch (expected 8 or 4 per
+ * vertex), a bin-count mismatch or a null argument, with nothing written. */
+#define GP_MULT_BINS 17
+#define GP_SOLE_BINS 32
+#define GP_SOLE_COLS 4
+int gp_track_mult(gp_ctx* ctx, int32_t on);
+int gp_read_mult_hist(gp_ctx* ctx, uint64_t* hist, int32_t bins);
+int gp_read_sole_bins(gp_ctx* ctx, uint64_t* out, int32_t bins);
 
 /* Checkpoints (no reference counterpart -- the
  * reference's peers keep no state across restarts).  Taken between rounds:
