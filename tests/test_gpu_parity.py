@@ -12,6 +12,8 @@ import os
 import numpy as np
 import pytest
 
+import raw_csr
+
 pytestmark = pytest.mark.gpu
 
 STAT_KEYS = ("injected", "lost", "new_bits", "receivers", "sends", "active", "crashed",
@@ -546,24 +548,7 @@ def test_raw_csr_self_loops_and_repeated_arcs(pkg, oracle, mode):
     count as links in the sends (deg) but can never bring a vertex anything
     it does not hold; unsorted in-lists; W = 2 rows, hubs split at 64."""
     push_ratio, unfiltered_pct, flat_max_words, arc_mask = mode
-    g0 = pkg.overlay.barabasi_albert(3000, 3, seed=41)
-    rng = np.random.default_rng(41)
-    src, dst = g0.arcs()
-    loops = rng.choice(g0.n, 300, replace=False)
-    again = rng.choice(src.size, 2000, replace=False)   # repeated arcs, both directions
-    s = np.concatenate([src, loops, src[again], dst[again]])
-    d = np.concatenate([dst, loops, dst[again], src[again]])
-    order = rng.permutation(s.size)   # in-lists in no particular order
-    s, d = s[order], d[order]
-    rp = np.zeros(g0.n + 1, np.int64)
-    np.add.at(rp, d + 1, 1)
-    rp = np.cumsum(rp)
-    col = np.empty(s.size, np.int32)
-    cur = rp[:-1].copy()
-    for u, v in zip(s.tolist(), d.tolist()):
-        col[cur[v]] = u
-        cur[v] += 1
-    g = pkg.CSR(g0.n, rp, col, False)
+    g = raw_csr.loops_and_repeats(pkg)
     origin = pkg.overlay.random_origins(g.n, 100, seed=41)
     inject = (np.arange(100) % 3).astype(np.int32)
     kw = dict(push_ratio=push_ratio, unfiltered_pct=unfiltered_pct, flat_max_words=flat_max_words,
