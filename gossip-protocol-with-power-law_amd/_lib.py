@@ -34,6 +34,8 @@ DELAY_BINS, DELAY_COLS = 32, 5                        # gp_read_delay_bins: degr
 SOLE_SENT, SOLE_RECV = 24, 25                         # delivery multiplicity (gp_track_mult)
 MULT_BINS = 17                                        # gp_read_mult_hist: 0 .. 15 deliverers, 16 or more
 SOLE_BINS, SOLE_COLS = 32, 4                          # gp_read_sole_bins: degree bins x columns
+DELAY_DIST = 26                                       # per-peer delay distributions (gp_track_delay_dist)
+DELAY_DIST_BINS = 16                                  # its columns: delays 0 .. 14, 15 or more
 # gp_shard_info transports
 XPORT_NONE, XPORT_RCCL, XPORT_HOST = 0, 1, 2
 
@@ -155,6 +157,8 @@ SIGNATURES = {
     "gp_read_link_hist": (ctypes.c_int, [_P, _P, _I32]),
     "gp_track_delay": (ctypes.c_int, [_P, _I32]),
     "gp_read_delay_bins": (ctypes.c_int, [_P, _P, _I32]),
+    "gp_track_delay_dist": (ctypes.c_int, [_P, _I32]),
+    "gp_read_delay_dist_bins": (ctypes.c_int, [_P, _P, _I32]),
     "gp_track_mult": (ctypes.c_int, [_P, _I32]),
     "gp_read_mult_hist": (ctypes.c_int, [_P, _P, _I32]),
     "gp_read_sole_bins": (ctypes.c_int, [_P, _P, _I32]),

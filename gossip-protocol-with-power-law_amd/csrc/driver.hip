@@ -621,7 +621,8 @@ static int round_launch(Ctx* c) {
   GP_TRY(mult_count_round(c));    // (... gp_track_mult)
   GP_TRY(fresh_curve_count_round(c));   // (... gp_track_fresh_curve)
   GP_TRY(link_count_round(c));   // (... gp_track_link_fresh)
-  return delay_count_round(c);   // (... gp_track_delay; all after expand_ms ends: round_ms carries them)
+  GP_TRY(delay_count_round(c));   // (... gp_track_delay)
+  return delay_dist_count_round(c);   // (... gp_track_delay_dist; all after expand_ms ends: round_ms carries them)
 }
 
 // X_r over RCCL.  One rank: the counters' all-reduce is the whole exchange.
@@ -1004,6 +1005,8 @@ int gp_read(gp_ctx* c, int32_t what, void* host, int64_t bytes) {
     case GP_DELAY_SUM:
     case GP_DELAY_MAX:   // per-peer receipt delays (delay.hip)
       return delay_read(c, what, host, bytes);
+    case GP_DELAY_DIST:   // per-peer delay distributions (delay_dist.hip)
+      return delay_dist_read(c, host, bytes);
     case GP_SOLE_SENT:
     case GP_SOLE_RECV:   // delivery multiplicity (mult.hip)
       return mult_read(c, what, host, bytes);

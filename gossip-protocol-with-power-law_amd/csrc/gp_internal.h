@@ -205,7 +205,18 @@ struct Ctx {
   bool delay_want = false, delay_alloc = false, delay_on = false, delay_valid = false;
   bool delay_force_rows = false;          // GP_DELAY_ROWS=1 at gp_create: the row pass for a one-round table too
   bool delay_by_rows() const { return delay_uniform < 0 || delay_force_rows; }
-  bool delay_needs_rows() const { return delay_want && delay_by_rows(); }
+  // per-peer delay distributions (delay_dist.hip): the same
+  // receipts per delay value, u16 [nloc][16] (delays 0 .. 14, 15 or more).  The
+  // flags are the receipt delays'; the two records are independent, share
+  // delay_uniform / delay_force_rows, and either one with a table of several
+  // inject rounds makes alloc_state keep the frontier rows (delay_alloc)
+  uint16_t* d_ddist = nullptr;            // [nloc][16]
+  u64* d_ddist_planes = nullptr;          // [8][W] inject-round planes of the context's table
+  u64* d_ddist_bins = nullptr;            // [32][16] gp_read_delay_dist_bins' device result
+  uint64_t ddist_present[4] = {0, 0, 0, 0};   // the table's inject rounds as a 256-bit set (delay_dist.h)
+  size_t ddist_rows = 0;                  // vertices the array holds
+  bool ddist_want = false, ddist_on = false, ddist_valid = false;
+  bool delay_needs_rows() const { return (delay_want || ddist_want) && delay_by_rows(); }
   // delivery multiplicity (mult.hip): how many in-neighbours
   // delivered each first receipt -- the histogram of that number, and per peer
   // the receipts with one deliverer, as receiver and as that deliverer.  The
@@ -478,6 +489,12 @@ int delay_count_round(Ctx* c);                 // after E_r: the delays of round
 void delay_restored(Ctx* c, int32_t round);    // gp_checkpoint_load: a run past round 0 lost its record
 bool delay_env_rows();                         // GP_DELAY_ROWS=1 in the environment
 int delay_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_DELAY_SUM / GP_DELAY_MAX
+// delay_dist.hip
+int delay_dist_reset(Ctx* c);                  // gp_reset: gp_track_delay_dist takes effect; the record (or none), cleared
+void delay_dist_free(Ctx* c);
+int delay_dist_count_round(Ctx* c);            // after E_r: round r's first receipts per receiver and delay value
+void delay_dist_restored(Ctx* c, int32_t round);   // gp_checkpoint_load: a run past round 0 lost its record
+int delay_dist_read(Ctx* c, void* host, int64_t bytes);   // GP_DELAY_DIST
 // mult.hip
 int mult_reset(Ctx* c);                        // gp_reset: gp_track_mult takes effect; the record (or none), cleared
 void mult_free(Ctx* c);

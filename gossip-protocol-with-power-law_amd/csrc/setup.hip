@@ -254,6 +254,7 @@ static void free_state(Ctx* c) {
   fresh_curve_free(c);
   link_free(c);
   delay_free(c);
+  delay_dist_free(c);
   mult_free(c);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
@@ -344,7 +345,7 @@ static int alloc_state(Ctx* c) {
   // partition, which sends owned vertices' new bits: the owned rows only (a
   // ghost's slot row is its frontier); the spread curve counts them too, and
   // the fresh-delivery passes (fresh.hip, fresh_curve.hip, link.hip) intersect them
-  // (the receipt delays read the receivers' own new rows, delay.hip -- unless every message starts in one round)
+  // (the receipt delays and their distributions read the receivers' own new rows, delay.hip, delay_dist.hip -- unless every message starts in one round)
   const bool frx_record = c->cfg.track_msg_forwards || c->curve_want || c->fresh_want || c->fresh_curve_want ||
                           c->link_want || c->delay_needs_rows() || c->mult_want;   // (and mult.hip)
   c->frx_rows = c->local ? c->nloc() : (frx_record ? c->n_alloc : 0);
@@ -619,6 +620,7 @@ void gp_destroy(gp_ctx* c) {
   fresh_curve_free(c);
   link_free(c);
   delay_free(c);
+  delay_dist_free(c);
   mult_free(c);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
@@ -895,7 +897,7 @@ int gp_reset(gp_ctx* c) {
   // rows, the count buffer)
   if (!state_ready(c) || c->curve_alloc != c->curve_want || c->fresh_alloc != c->fresh_want ||
       c->fresh_curve_alloc != c->fresh_curve_want || c->link_alloc != c->link_want ||
-      c->delay_alloc != c->delay_needs_rows() ||   // (gp_track_delay: rows only for a table of several inject rounds)
+      c->delay_alloc != c->delay_needs_rows() ||   // (gp_track_delay, gp_track_delay_dist: rows only for a table of several inject rounds)
       c->mult_alloc != c->mult_want)               // (gp_track_mult)
     GP_TRY(alloc_state(c));
   if (!c->done_at_valid) {
@@ -948,6 +950,7 @@ int gp_reset(gp_ctx* c) {
   GP_TRY(fresh_curve_reset(c));   // (and gp_track_fresh_curve)
   GP_TRY(link_reset(c));          // (and gp_track_link_fresh)
   GP_TRY(delay_reset(c));         // (and gp_track_delay)
+  GP_TRY(delay_dist_reset(c));    // (and gp_track_delay_dist)
   GP_TRY(mult_reset(c));          // (and gp_track_mult)
   GP_HIP(hipStreamSynchronize(s));
   return 0;

@@ -490,6 +490,26 @@ class GossipEngine:
         check(self._lib.gp_read_delay_bins(self._ctx, _ptr(buf), buf.shape[0]))
         return buf
 
+    # -- per-peer delay distributions (csrc/delay_dist.hip; helpers in latency.py)
+    def track_delay_dist(self, on=True):
+        """gp_track_delay_dist: keep, per owned peer, its receipts per delay
+        value (receipt round - inject round) from the next reset() on.
+        Independent of track_delay()."""
+        check(self._lib.gp_track_delay_dist(self._ctx, 1 if on else 0))
+
+    def delay_dist(self):
+        """u16 [owned vertices][16]: v's receipts since reset() with delay d in
+        column d -- 0: injected at v, 1 .. 14 exact, 15: 15 rounds or later.
+        Every row sums to seenpop()[v] (latency.dist_quantile reads it)."""
+        return self._read(_lib.DELAY_DIST, np.empty((self.nloc(), _lib.DELAY_DIST_BINS), dtype=np.uint16))
+
+    def delay_dist_bins(self):
+        """u64 [32][16]: the rows summed by degree bin, computed on the device
+        (latency.dist_bins is its numpy twin, latency.dist_by_degree reads it)."""
+        buf = np.zeros((_lib.DELAY_BINS, _lib.DELAY_DIST_BINS), dtype=np.uint64)
+        check(self._lib.gp_read_delay_dist_bins(self._ctx, _ptr(buf), buf.shape[0]))
+        return buf
+
     # -- delivery multiplicity (csrc/mult.hip; helpers in fragility.py) -------
     def track_mult(self, on=True):
         """gp_track_mult: keep, from the next reset() on, how many in-neighbours

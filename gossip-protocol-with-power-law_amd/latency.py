@@ -10,7 +10,14 @@ and delay_max a sampled eccentricity.  These helpers answer the power-law
 question -- do hubs hear early and leaves late? -- and tie the record to the
 spread curve.  Pure numpy; every function validates its shapes and raises
 ValueError on arrays that cannot belong to one run.
+
+The dist_* helpers read the per-peer delay distributions
+(GossipEngine.delay_dist() / delay_dist_bins(), csrc/delay_dist.hip): the same
+receipts per delay value, which give each peer's and each degree bin's median
+and tail.
 """
+from fractions import Fraction
+
 import numpy as np
 
 BINS, COLS = 32, 5   # gp_read_delay_bins: degree bins x (peers, reached, receipts, delay sum, delay max)
@@ -166,3 +173,127 @@ def total_delay(curve, inject_round=None):
     single-rank run exactly sum(delay_sum())."""
     c, d = _curve(curve, inject_round)
     return int((np.where(d >= 0, d, 0) * c).sum())
+
+
+# -- delay distributions (delay_dist(), delay_dist_bins()) ------------------------
+
+DIST_BINS = 16       # columns of a delay_dist row: delays 0 .. 14, 15 or more
+DIST_LAST = DIST_BINS - 1
+
+
+def _dist(dist, name="dist", rows=None):
+    a = np.asarray(dist)
+    if a.ndim != 2 or a.shape[1] != DIST_BINS or a.dtype.kind not in "ui":
+        raise ValueError(f"{name} must be an integer array [rows][{DIST_BINS}]")
+    a = a.astype(np.int64)
+    if rows is not None and a.shape[0] != rows:
+        raise ValueError(f"{name} has {a.shape[0]} rows, expected {rows}: arrays of different runs")
+    if a.size and a.min() < 0:
+        raise ValueError(f"{name} is negative somewhere")
+    return a
+
+
+def dist_quantile(dist, q, flag=False):
+    """float64 [rows]: the q-quantile of every row's delays by the lower-value
+    rule -- the smallest d with cumsum(row)[d] >= ceil(q * total), at least the
+    first receipt.  NaN for a row without receipts (a peer never reached).  A
+    quantile that falls in the last column is only known to be >= 15 and is
+    returned as 15; flag=True returns (values, saturated) with a bool array
+    that marks those rows.  Works on delay_dist() and on a delay_dist_bins()
+    table alike."""
+    a = _dist(dist)
+    if not 0 <= q <= 1:
+        raise ValueError("q must be in [0, 1]")
+    f = Fraction(q).limit_denominator(10 ** 9)   # (0.9 * 10 is not 9 in floating point)
+    total = a.sum(axis=1)
+    rank = np.maximum((f.numerator * total + f.denominator - 1) // f.denominator, 1)
+    idx = (np.cumsum(a, axis=1) < rank[:, None]).sum(axis=1)   # first column whose cumsum reaches the rank
+    out = np.full(a.shape[0], np.nan)
+    ok = total > 0
+    out[ok] = idx[ok]
+    return (out, ok & (idx == DIST_LAST)) if flag else out
+
+
+def dist_bins(deg, dist):
+    """uint64 [32][16], the numpy twin of GossipEngine.delay_dist_bins(): row b
+    sums the rows of the vertices with degree_bin(deg) = b."""
+    a = _dist(dist)
+    b = degree_bin(_vec(deg, "deg", a.shape[0]))
+    out = np.zeros((BINS, DIST_BINS), np.int64)
+    for k in np.unique(b):   # (integer adds, a bin at a time: np.add.at is slow on millions of rows)
+        out[k] = a[b == k].sum(axis=0)
+    return out.astype(np.uint64)
+
+
+def _dist_table(table):
+    t = np.asarray(table)
+    if t.shape != (BINS, DIST_BINS) or t.dtype.kind not in "ui":
+        raise ValueError(f"a delay_dist_bins table is an integer array [{BINS}][{DIST_BINS}]")
+    if t.size and t.min() < 0:
+        raise ValueError("a delay_dist_bins table is negative somewhere")
+    return t.astype(np.int64)
+
+
+def dist_by_degree(table, qs=(0.5, 0.9, 0.99)):
+    """The rows of a delay_dist_bins table that hold receipts, as a list of
+    dicts: bin, the bin's degree range [deg_lo, deg_hi] (as by_degree),
+    receipts, mean_delay (the last column taken as 15: a lower bound when
+    `saturated`), one key per quantile -- "p50", "p90", "p99" for the default
+    qs -- and saturated: whether any of them fell in the last column."""
+    t = _dist_table(table)
+    cols = [dist_quantile(t, q, flag=True) for q in qs]
+    out = []
+    for b in range(BINS):
+        receipts = int(t[b].sum())
+        if receipts == 0:
+            continue
+        row = dict(bin=b, deg_lo=0 if b == 0 else 1 << b, deg_hi=1 if b == 0 else (2 << b) - 1, receipts=receipts,
+                   mean_delay=int((t[b] * np.arange(DIST_BINS)).sum()) / receipts)
+        for q, (val, _) in zip(qs, cols):
+            row[f"p{100 * q:g}"] = int(val[b])
+        row["saturated"] = any(bool(sat[b]) for _, sat in cols)
+        out.append(row)
+    return out
+
+
+def dist_combine(arrays):
+    """int64: the element-wise sum of several contexts' delay_dist() arrays (or
+    delay_dist_bins() tables) -- message shards of one vertex set.  Added in
+    int64: nothing promises that the shards' u16 cells add up within u16."""
+    arrs = [np.asarray(a) for a in arrays]
+    if not arrs:
+        raise ValueError("no array")
+    for a in arrs:
+        if a.ndim != 2 or a.shape != arrs[0].shape or a.shape[1] != DIST_BINS or a.dtype.kind not in "ui":
+            raise ValueError(f"shards' arrays are integer arrays of one shape [rows][{DIST_BINS}]")
+    out = np.zeros(arrs[0].shape, np.int64)
+    for a in arrs:
+        out += a.astype(np.int64)
+    return out
+
+
+def dist_check(dist, seenpop, delay_sum=None, delay_max=None):
+    """Raise ValueError unless the arrays can belong to one run: every row of
+    dist sums to seenpop; with delay_sum, a row with an empty last column has
+    sum d * dist[d] = delay_sum and any other at most delay_sum; with
+    delay_max, the largest occupied column is delay_max, or delay_max >= 15
+    where the last column is occupied."""
+    sp = _vec(seenpop, "seenpop")
+    a = _dist(dist, rows=sp.size)
+    if (a.sum(axis=1) != sp).any():
+        raise ValueError("a row of dist does not sum to seenpop: arrays of different runs")
+    open_ = a[:, DIST_LAST] == 0
+    if delay_sum is not None:
+        ds = _vec(delay_sum, "delay_sum", sp.size)
+        weighted = (a * np.arange(DIST_BINS)).sum(axis=1)
+        if (weighted[open_] != ds[open_]).any():
+            raise ValueError("sum d * dist[d] is not delay_sum where no delay reached 15: arrays of different runs")
+        if (weighted[~open_] > ds[~open_]).any():
+            raise ValueError("sum d * dist[d] exceeds delay_sum: arrays of different runs")
+    if delay_max is not None:
+        dm = _vec(delay_max, "delay_max", sp.size)
+        top = np.where(a > 0, np.arange(DIST_BINS)[None, :], 0).max(axis=1, initial=0)
+        if (top[open_] != dm[open_]).any():
+            raise ValueError("the largest occupied column is not delay_max: arrays of different runs")
+        if (dm[~open_] < DIST_LAST).any():
+            raise ValueError("receipts of 15 rounds or later with a delay_max below 15: arrays of different runs")

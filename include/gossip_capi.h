@@ -202,7 +202,9 @@ typedef enum gp_what {
   GP_DELAY_MAX = 23,  /* u8  [vend-vbegin]  v's largest receipt delay (0: none)      */
   /* delivery multiplicity (gp_track_mult below) */
   GP_SOLE_SENT = 24,  /* u64 [n]  first receipts peer u alone delivered, over its out-arcs */
-  GP_SOLE_RECV = 25   /* u32 [n]  first receipts of peer v that had one deliverer     */
+  GP_SOLE_RECV = 25,  /* u32 [n]  first receipts of peer v that had one deliverer     */
+  /* per-peer delay distributions (gp_track_delay_dist below) */
+  GP_DELAY_DIST = 26  /* u16 [vend-vbegin][GP_DELAY_DIST_BINS]  v's receipts per delay value */
 } gp_what;
 
 int gp_abi_version(void);
@@ -575,6 +577,51 @@ int gp_read_link_hist(gp_ctx* ctx, uint64_t* hist, int32_t bins);
 #define GP_DELAY_COLS 5
 int gp_track_delay(gp_ctx* ctx, int32_t on);
 int gp_read_delay_bins(gp_ctx* ctx, uint64_t* out, int32_t bins);
+
+/* Per-peer delay distributions: the same receipts per
+ * delay value, so that a peer's median and tail can be read, not its mean and
+ * maximum alone.  For an owned vertex v, over the messages k of the context's
+ * table, with D = GP_DELAY_DIST_BINS:
+ *   GP_DELAY_DIST  delay_dist[v][d] = #{ k : first[v][k] != 255,
+ *                  min(first[v][k] - inject_round[k], D - 1) = d }     u16 [vend - vbegin][D]
+ * Columns 1 .. D - 2 are exact, column D - 1 is "D - 1 rounds or later", column 0
+ * holds the receipts with delay 0: the injections at v at an up origin.  Every
+ * cell is <= m <= 4096.  sum_d delay_dist[v][d] = GP_SEENPOP[v] at every read
+ * between rounds: column 0 is computed by the reads, on the device, as seenpop
+ * minus the other columns.  With gp_track_delay also on, a peer with an empty
+ * last column has sum_d d * delay_dist[v][d] = delay_sum[v] and its largest
+ * occupied column is delay_max[v]; otherwise the weighted sum (the last column
+ * at D - 1) is <= delay_sum[v] and delay_max[v] >= D - 1.  Over a single-rank
+ * run with gp_track_curve the column sums are the run's receipts per delay.
+ * Expansion receipts count when they happen (a receiver that crashes in the
+ * next round still received).  Scope as the receipt delays': totals since
+ * gp_reset, readable between rounds; a context that runs a block of a message
+ * table holds its own messages' receipts and the shards' arrays add element by
+ * element (the host adds them, in a wider type); a vertex-partitioned context
+ * keeps the record for its owned vertices.
+ *
+ * gp_read_delay_dist_bins computes, on the device and from the current record,
+ * a u64 [GP_DELAY_BINS][GP_DELAY_DIST_BINS] table: row b sums the rows of the
+ * owned vertices with bin(in-list length) = b (gp_read_delay_bins' bins),
+ * column 0 included; sum_d table[b][d] is gp_read_delay_bins' receipts column.
+ * `bins` must be GP_DELAY_BINS (else GP_EINVAL, nothing written).
+ *
+ * gp_track_delay_dist(on) takes effect at the next gp_reset, which allocates
+ * (and clears) 32 bytes per owned vertex; off, nothing is allocated or
+ * launched, and turning it off frees the array at the next gp_reset.  It is
+ * independent of gp_track_delay: either, both or neither.  Every round then
+ * adds one pass after the expansion, over the receivers' own new rows or, when
+ * every message of the table has the same inject round, over the per-vertex
+ * counts alone: such a table keeps no frontier rows for this record
+ * (GP_DELAY_ROWS=1 takes the row pass here too).
+ *
+ * Reads: GP_ENOTRACK before tracking took effect; GP_ESTATE for a run restored
+ * from a checkpoint past round 0, until the next gp_reset; GP_EINVAL on a
+ * byte-count mismatch (expected 2 * GP_DELAY_DIST_BINS per owned vertex), a
+ * bin-count mismatch or a null argument. */
+#define GP_DELAY_DIST_BINS 16
+int gp_track_delay_dist(gp_ctx* ctx, int32_t on);
+int gp_read_delay_dist_bins(gp_ctx* ctx, uint64_t* out, int32_t bins);
 
 /* Delivery multiplicity: how fragile the flood was.
  * The fresh-delivery records are sums over deliverers; this one keeps the
