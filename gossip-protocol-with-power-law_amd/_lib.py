@@ -36,6 +36,8 @@ MULT_BINS = 17                                        # gp_read_mult_hist: 0 .. 
 SOLE_BINS, SOLE_COLS = 32, 4                          # gp_read_sole_bins: degree bins x columns
 DELAY_DIST = 26                                       # per-peer delay distributions (gp_track_delay_dist)
 DELAY_DIST_BINS = 16                                  # its columns: delays 0 .. 14, 15 or more
+WATCH_FIRST, WATCH_ARRIVAL, WATCH_PTR = 27, 28, 29    # watched peers (gp_watch)
+WATCH_MAX_PEERS = 65536
 # gp_shard_info transports
 XPORT_NONE, XPORT_RCCL, XPORT_HOST = 0, 1, 2
 
@@ -162,6 +164,9 @@ SIGNATURES = {
     "gp_track_mult": (ctypes.c_int, [_P, _I32]),
     "gp_read_mult_hist": (ctypes.c_int, [_P, _P, _I32]),
     "gp_read_sole_bins": (ctypes.c_int, [_P, _P, _I32]),
+    "gp_watch": (ctypes.c_int, [_P, _I32, _P, _I64]),
+    "gp_watch_info": (ctypes.c_int, [_P, _PI32, _PI64, _PI64]),
+    "gp_read_watch_peer": (ctypes.c_int, [_P, _I32, _P, _P, _I64]),
     "gp_checkpoint_size":(ctypes.c_int, [_P, _PI64]),
     "gp_checkpoint_save": (ctypes.c_int, [_P, _P, _I64]),
     "gp_checkpoint_load": (ctypes.c_int, [_P, _P, _I64]),

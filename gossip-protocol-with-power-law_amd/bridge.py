@@ -22,6 +22,12 @@ every 5 rounds, Peer.py:396-408).  Each `step()` runs one device round and
 renders what the reference's sockets would have carried in that second: the
 gossip lines each peer receives for the first time, the dead-node reports
 live peers send to the seed, and the seed's log lines for them.
+
+With `watch=[identities]` the bridge serves those peers alone, from the engine's
+watched-peers record (GossipEngine.watch, watch.py) instead of the whole
+first-receipt matrix: their deliveries, and every line that arrived at them
+with the peer it came from -- the entries of their logs (Peer.py:206) -- so a
+bridge in front of a large overlay can stand in for a few real peers.
 """
 import ast
 import json
@@ -29,6 +35,7 @@ import json
 import numpy as np
 
 from . import peer as wire
+from . import watch as watchlog
 from .overlay import CSR
 from .seed import SeedRegistry
 
@@ -85,13 +92,15 @@ def parse_subset(line):
 
 class ProtocolBridge:
     def __init__(self, seed=("127.0.0.1", 0), device=0, messages_per_peer=wire.MESSAGES_PER_PEER,
-                 period=wire.GOSSIP_PERIOD_ROUNDS, **engine_cfg):
+                 period=wire.GOSSIP_PERIOD_ROUNDS, watch=None, **engine_cfg):
         self.registry = SeedRegistry(*seed)
         self.seed = tuple(seed)
         self.device = device
         self.per_peer = messages_per_peer
         self.period = period
-        self.engine_cfg = dict(track_first=1, track_digest=1)
+        self.watch = None if watch is None else [tuple(w) for w in watch]
+        # (the watched peers' rows replace the n x m first-receipt matrix)
+        self.engine_cfg = dict(track_digest=1) if self.watch is not None else dict(track_first=1, track_digest=1)
         self.engine_cfg.update(engine_cfg)
         self.peers = []            # registration order = vertex id
         self.vertex = {}           # identity -> vertex id
@@ -144,9 +153,18 @@ class ProtocolBridge:
         self.engine = GossipEngine(self.device, **self.engine_cfg)
         self.engine.load_graph(self.overlay())
         self.engine.set_messages(self.origin, self.inject)
+        if self.watch is not None:
+            self._wv = [self.vertex[w] for w in self.watch]
+            self.engine.watch(self._wv)
         self.engine.reset()
         self.round = 0
-        self._first = np.full((len(self.peers), len(self.origin)), 255, np.uint8)
+        if self.watch is not None:
+            ptr, self._wsender = watchlog.arcs(self.overlay(), self._wv)
+            self._wslot = np.repeat(np.arange(len(self._wv)), np.diff(ptr))
+            self._first = np.full((len(self._wv), len(self.origin)), 255, np.uint8)
+            self._arrival = np.full((self._wsender.size, len(self.origin)), 255, np.uint8)
+        else:
+            self._first = np.full((len(self.peers), len(self.origin)), 255, np.uint8)
 
     def crash(self, ident):
         """Silent mode for one peer (Peer.py:437-439): from the next round on it
@@ -161,13 +179,25 @@ class ProtocolBridge:
     def step(self):
         """One device round, rendered: deliveries [(to, line)] of this round's
         first receipts, reports [(reporter, line)] sent to the seed, and the
-        seed's log lines for them."""
+        seed's log lines for them.  A watching bridge renders the deliveries of
+        its watched peers only and adds arrivals [(to, from, line, fresh)]: every
+        gossip line that reached one of them in this round, with the peer it
+        came from and whether it was news."""
         st = self.engine.round()
         r = st["round"]
-        first = self.engine.first()
+        watched = self.watch is not None
+        first = self.engine.watch_first() if watched else self.engine.first()
         new = np.argwhere((first != self._first) & (first == r + 1))   # receipt round r + 1
         self._first = first
-        deliveries = [(self.peers[v], self.gossip_line(m)) for v, m in new.tolist()]
+        who = self._wv if watched else range(len(self.peers))
+        deliveries = [(self.peers[who[v]], self.gossip_line(m)) for v, m in new.tolist()]
+        arrivals = None
+        if watched:
+            arr = self.engine.watch_arrival()
+            came = np.argwhere(arr != self._arrival)
+            self._arrival = arr
+            arrivals = [(self.peers[who[self._wslot[a]]], self.peers[int(self._wsender[a])], self.gossip_line(m),
+                         bool(arr[a, m] == first[self._wslot[a], m])) for a, m in came.tolist()]
         rep, total = self.engine.reports(max(int(st["reports"]), 1))
         if st["overflow"] or total != len(rep):
             # a subset of the Dead Node lines would let the seed log drift from
@@ -180,8 +210,11 @@ class ProtocolBridge:
         for _, line in reports:
             self.handle(line)
         self.round = r + 1
-        return {"round": r, "stats": st, "deliveries": deliveries, "reports": reports,
-                "seed_log": self.registry.logs[n_log:]}
+        out = {"round": r, "stats": st, "deliveries": deliveries, "reports": reports,
+               "seed_log": self.registry.logs[n_log:]}
+        if watched:
+            out["arrivals"] = arrivals
+        return out
 
     def run(self, max_rounds=254):
         last = int(self.inject.max())

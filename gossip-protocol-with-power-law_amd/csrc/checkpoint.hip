@@ -177,7 +177,7 @@ int gp_checkpoint_load(gp_ctx* c, const void* host, int64_t bytes) {
     return set_error(GP_EINVAL, "checkpoint of another partition");
   if (h.has_first != (c->cfg.track_first ? 1 : 0) || h.has_frx != (c->holds_frx() ? 1 : 0))
     return set_error(GP_EINVAL, "checkpoint tracks other outputs (track_first / frontier rows: track_msg_forwards, "
-                                "gp_track_curve, gp_track_fresh, gp_track_fresh_curve, gp_track_link_fresh, gp_track_delay, gp_track_delay_dist, gp_track_mult)");
+                                "gp_track_curve, gp_track_fresh, gp_track_fresh_curve, gp_track_link_fresh, gp_track_delay, gp_track_delay_dist, gp_track_mult, gp_watch)");
   GP_HIP(hipSetDevice(c->device));
   // the component targets (cmask rows) of this message set; computing them
   // touches no run state that could be in progress (set_messages invalidated it)
@@ -247,6 +247,7 @@ int gp_checkpoint_load(gp_ctx* c, const void* host, int64_t bytes) {
   delay_restored(c, h.round);  // (nor the receipt delays, delay.hip)
   delay_dist_restored(c, h.round);   // (nor their distributions, delay_dist.hip)
   mult_restored(c, h.round);   // (nor the delivery multiplicity, mult.hip)
+  watch_restored(c, h.round);  // (nor the watched peers' arrivals, watch.hip)
   return 0;
 }
 

@@ -622,7 +622,8 @@ static int round_launch(Ctx* c) {
   GP_TRY(fresh_curve_count_round(c));   // (... gp_track_fresh_curve)
   GP_TRY(link_count_round(c));   // (... gp_track_link_fresh)
   GP_TRY(delay_count_round(c));   // (... gp_track_delay)
-  return delay_dist_count_round(c);   // (... gp_track_delay_dist; all after expand_ms ends: round_ms carries them)
+  GP_TRY(delay_dist_count_round(c));   // (... gp_track_delay_dist)
+  return watch_count_round(c);   // (... gp_watch; all after expand_ms ends: round_ms carries them)
 }
 
 // X_r over RCCL.  One rank: the counters' all-reduce is the whole exchange.
@@ -1010,6 +1011,10 @@ int gp_read(gp_ctx* c, int32_t what, void* host, int64_t bytes) {
     case GP_SOLE_SENT:
     case GP_SOLE_RECV:   // delivery multiplicity (mult.hip)
       return mult_read(c, what, host, bytes);
+    case GP_WATCH_FIRST:
+    case GP_WATCH_ARRIVAL:
+    case GP_WATCH_PTR:   // watched peers (watch.hip)
+      return watch_read(c, what, host, bytes);
     case GP_SEENPOP:
       if (!run) return set_error(GP_ESTATE, "no run state");
       GP_TRY(need(nl * 4));

@@ -229,9 +229,29 @@ struct Ctx {
   u64* d_mult_hub_sole = nullptr;         // [n_hubs][W] the hubs' sole masks of one round
   size_t mult_rows = 0, mult_scratch_words = 0, mult_hub_words = 0;   // what the arrays were sized for
   bool mult_want = false, mult_alloc = false, mult_on = false, mult_valid = false;
+  // watched peers (watch.hip): the arrival log of a caller-chosen
+  // list of peers, one byte per (in-arc, message) and per (peer, message).
+  // h_watch_want is what gp_watch set, for the next gp_reset; h_watch_v /
+  // h_watch_ptr are the list in force and its arc offsets.  watch_alloc is
+  // whether alloc_state sized the frontier rows for it, watch_on what the run
+  // since the last gp_reset keeps (single-rank contexts only), watch_valid falls
+  // when a checkpoint restores the run past round 0
+  std::vector<int32_t> h_watch_want, h_watch_v;
+  std::vector<int64_t> h_watch_ptr;       // [K + 1]
+  int64_t watch_max_bytes = 0;            // gp_watch's budget for the two byte arrays
+  int32_t* d_watch_v = nullptr;           // [K]
+  int64_t* d_watch_ptr = nullptr;         // [K + 1]
+  int32_t* d_watch_col = nullptr;         // [A] senders of the watched arcs (a compact copy of the in-lists)
+  int32_t* d_watch_slot = nullptr;        // [A] their receivers' slots
+  uint8_t* d_watch_first = nullptr;       // [K][W * 64], 255 = never
+  uint8_t* d_watch_arrival = nullptr;     // [A][W * 64]
+  int64_t watch_arcs = 0;                 // A
+  int32_t watch_words = 0;                // the row width the arrays were made for
+  bool watch_alloc = false, watch_on = false, watch_valid = false;
+  bool watch_want() const { return !h_watch_want.empty(); }
   bool holds_frx() const {
     return cfg.track_msg_forwards != 0 || local || curve_want || fresh_want || fresh_curve_want || link_want ||
-           delay_needs_rows() || mult_want;
+           delay_needs_rows() || mult_want || watch_want();
   }
   uint32_t* d_fpop[2] = {nullptr, nullptr};    // [n_alloc]
   int cur = 0;
@@ -501,6 +521,13 @@ void mult_free(Ctx* c);
 int mult_count_round(Ctx* c);                  // after E_r: the deliverer counts of round r's first receipts
 void mult_restored(Ctx* c, int32_t round);     // gp_checkpoint_load: a run past round 0 lost its record
 int mult_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_SOLE_SENT / GP_SOLE_RECV
+// watch.hip
+int watch_reset(Ctx* c);                       // gp_reset: gp_watch's list takes effect; the record (or none), filled with 255
+void watch_free(Ctx* c);
+void watch_forget(Ctx* c);                     // a new overlay: the list's ids were the old one's
+int watch_count_round(Ctx* c);                 // after E_r: round r's arrivals at the watched peers, link by link
+void watch_restored(Ctx* c, int32_t round);    // gp_checkpoint_load: a run past round 0 lost its record
+int watch_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_WATCH_FIRST / GP_WATCH_ARRIVAL / GP_WATCH_PTR
 // driver.hip: k_mkbits (and k_mksum) over fpop[cur], ahead of launch_expand
 int launch_activity_bits(Ctx* c, bool summary);
 // driver.hip: cnt[m] += the rows' bit m over rows [0, count) with guard[i] != 0 (the per-bit k_bitsum)

@@ -256,6 +256,7 @@ static void free_state(Ctx* c) {
   delay_free(c);
   delay_dist_free(c);
   mult_free(c);
+  watch_free(c);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_abits); dfree(&c->d_dbits); dfree(&c->d_lm); dfree(&c->d_lmw[0]); dfree(&c->d_lmw[1]); dfree(&c->d_sbits); dfree(&c->d_amask); dfree(&c->d_cml[0]); dfree(&c->d_cml[1]); dfree(&c->d_cmk[0]); dfree(&c->d_cmk[1]); dfree(&c->d_done_at);
@@ -309,6 +310,7 @@ static int components(Ctx* c) {
 
 int finish_graph(Ctx* c) {
   free_state(c);
+  watch_forget(c);   // (gp_watch's ids were checked against the overlay this one replaces)
   free_partition(c);   // a new overlay: partition again from the global CSR
   c->nnz_l = c->nnz;
   GP_TRY(dalloc(&c->d_deg_out, (size_t)c->n));
@@ -347,13 +349,15 @@ static int alloc_state(Ctx* c) {
   // the fresh-delivery passes (fresh.hip, fresh_curve.hip, link.hip) intersect them
   // (the receipt delays and their distributions read the receivers' own new rows, delay.hip, delay_dist.hip -- unless every message starts in one round)
   const bool frx_record = c->cfg.track_msg_forwards || c->curve_want || c->fresh_want || c->fresh_curve_want ||
-                          c->link_want || c->delay_needs_rows() || c->mult_want;   // (and mult.hip)
+                          c->link_want || c->delay_needs_rows() || c->mult_want ||   // (and mult.hip)
+                          c->watch_want();                                            // (and the watched peers, watch.hip)
   c->frx_rows = c->local ? c->nloc() : (frx_record ? c->n_alloc : 0);
   c->fresh_alloc = c->fresh_want;
   c->fresh_curve_alloc = c->fresh_curve_want;
   c->link_alloc = c->link_want;
   c->delay_alloc = c->delay_needs_rows();
   c->mult_alloc = c->mult_want;
+  c->watch_alloc = c->watch_want();
   dfree(&c->d_slot[2]);   // (re)allocated at the first parking, for this W
   c->carry = RoundCarry{};   // (new buffers carry nothing over; parking may be tried again)
   // S[0] | S[1] | accumulator rows of the owned receivers, one allocation
@@ -622,6 +626,7 @@ void gp_destroy(gp_ctx* c) {
   delay_free(c);
   delay_dist_free(c);
   mult_free(c);
+  watch_free(c);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_stats);
@@ -898,7 +903,8 @@ int gp_reset(gp_ctx* c) {
   if (!state_ready(c) || c->curve_alloc != c->curve_want || c->fresh_alloc != c->fresh_want ||
       c->fresh_curve_alloc != c->fresh_curve_want || c->link_alloc != c->link_want ||
       c->delay_alloc != c->delay_needs_rows() ||   // (gp_track_delay, gp_track_delay_dist: rows only for a table of several inject rounds)
-      c->mult_alloc != c->mult_want)               // (gp_track_mult)
+      c->mult_alloc != c->mult_want ||             // (gp_track_mult)
+      c->watch_alloc != c->watch_want())           // (gp_watch)
     GP_TRY(alloc_state(c));
   if (!c->done_at_valid) {
     GP_TRY(compute_done_at(c, c->n_groups));
@@ -952,6 +958,7 @@ int gp_reset(gp_ctx* c) {
   GP_TRY(delay_reset(c));         // (and gp_track_delay)
   GP_TRY(delay_dist_reset(c));    // (and gp_track_delay_dist)
   GP_TRY(mult_reset(c));          // (and gp_track_mult)
+  GP_TRY(watch_reset(c));         // (and gp_watch)
   GP_HIP(hipStreamSynchronize(s));
   return 0;
 }

@@ -542,6 +542,48 @@ class GossipEngine:
         check(self._lib.gp_read_sole_bins(self._ctx, _ptr(buf), buf.shape[0]))
         return buf
 
+    # -- watched peers (csrc/watch.hip; helpers in watch.py) -------------------
+    def watch(self, verts, max_bytes=0):
+        """gp_watch: keep, from the next reset() on, the arrival log of the
+        peers `verts` (distinct vertex ids; an empty list turns the record off)
+        -- one byte per (in-arc, message) and per (peer, message).  max_bytes
+        bounds the two arrays (0: 1 GiB); a refused call leaves the previous
+        list in force."""
+        v = np.ascontiguousarray(verts, dtype=np.int32).reshape(-1)
+        check(self._lib.gp_watch(self._ctx, int(v.size), _ptr(v) if v.size else None, int(max_bytes)))
+
+    def watch_info(self):
+        """(peers, arcs, bytes) of the list in force for the current run; 0s
+        when none is."""
+        k, a, b = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64()
+        check(self._lib.gp_watch_info(self._ctx, ctypes.byref(k), ctypes.byref(a), ctypes.byref(b)))
+        return k.value, a.value, b.value
+
+    def watch_ptr(self):
+        """i64 [K + 1]: slot s's watched arcs are [ptr[s], ptr[s + 1]), the
+        in-arcs of its peer in the in-CSR's order (watch.arcs is its numpy twin)."""
+        return self._read(_lib.WATCH_PTR, np.empty(self.watch_info()[0] + 1, dtype=np.int64))
+
+    def watch_first(self):
+        """u8 [K][m]: the watched peers' first-receipt rows, 255 = never."""
+        return self._read(_lib.WATCH_FIRST, np.empty((self.watch_info()[0], self.m), dtype=np.uint8))
+
+    def watch_arrival(self):
+        """u8 [A][m]: the receipt round of every message over every watched
+        in-arc since reset(), 255 = never (watch.lines reads it)."""
+        return self._read(_lib.WATCH_ARRIVAL, np.empty((self.watch_info()[1], self.m), dtype=np.uint8))
+
+    def watch_peer(self, slot):
+        """(first_row u8 [m], arrival u8 [deg][m]) of one slot, without reading
+        the whole record."""
+        ptr = self.watch_ptr()
+        slot = int(slot)
+        deg = int(ptr[slot + 1] - ptr[slot]) if 0 <= slot < ptr.size - 1 else 0
+        first = np.empty(self.m, dtype=np.uint8)
+        arr = np.empty((deg, self.m), dtype=np.uint8)
+        check(self._lib.gp_read_watch_peer(self._ctx, slot, _ptr(first), _ptr(arr), arr.nbytes))
+        return first, arr
+
     def _nv(self):   # per-vertex reads: the owned slice of a partitioned context
         return self.nloc() if self.nranks > 1 else self.n
 

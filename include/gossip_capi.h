@@ -204,7 +204,11 @@ typedef enum gp_what {
   GP_SOLE_SENT = 24,  /* u64 [n]  first receipts peer u alone delivered, over its out-arcs */
   GP_SOLE_RECV = 25,  /* u32 [n]  first receipts of peer v that had one deliverer     */
   /* per-peer delay distributions (gp_track_delay_dist below) */
-  GP_DELAY_DIST = 26  /* u16 [vend-vbegin][GP_DELAY_DIST_BINS]  v's receipts per delay value */
+  GP_DELAY_DIST = 26, /* u16 [vend-vbegin][GP_DELAY_DIST_BINS]  v's receipts per delay value */
+  /* watched peers (gp_watch below) */
+  GP_WATCH_FIRST = 27,   /* u8  [K][m]  first-receipt rows of the watched peers, 255 = never */
+  GP_WATCH_ARRIVAL = 28, /* u8  [A][m]  receipt round per watched in-arc and message, 255 = never */
+  GP_WATCH_PTR = 29      /* i64 [K+1]   first watched arc of every slot                      */
 } gp_what;
 
 int gp_abi_version(void);
@@ -682,6 +686,66 @@ int gp_read_delay_dist_bins(gp_ctx* ctx, uint64_t* out, int32_t bins);
 int gp_track_mult(gp_ctx* ctx, int32_t on);
 int gp_read_mult_hist(gp_ctx* ctx, uint64_t* hist, int32_t bins);
 int gp_read_sole_bins(gp_ctx* ctx, uint64_t* out, int32_t bins);
+
+/* Watched peers: the arrival log of a caller-chosen
+ * list of peers, link by link.  The reference's user-facing output is a log per
+ * peer: every gossip line that arrives is written down with the peer it came
+ * from and the time (Peer.py:206, Peer.py:286, through Peer.log, Peer.py:40-47).
+ * Forward-once means a sender puts each message on a link exactly once, so the
+ * whole arrival log of peer v is a [deg_in(v)][m] byte matrix: the round in which
+ * that link delivered that message, or never.
+ *
+ * The watch list is v_0 .. v_{K-1}: distinct global vertex ids in the caller's
+ * order; s is a peer's slot, A = sum_s deg_in(v_s), and watched arc
+ * a = watch_ptr[s] + i is the i-th arc of row v_s of the in-CSR as loaded or
+ * built (GP_ROW_PTR / GP_COL, GP_LINK_FRESH's indexing), with sender
+ * u = col[row_ptr[v_s] + i]:
+ *   GP_WATCH_FIRST    watch_first[s][k]   = first[v_s][k]                   u8 [K][m]
+ *   GP_WATCH_ARRIVAL  watch_arrival[a][k] = r + 1  if k in frontier_r(u)
+ *                                                  and v_s is up in E_r     u8 [A][m]
+ *   GP_WATCH_PTR      watch_ptr[s]                                          i64 [K + 1]
+ * 255 = never; a cell is the receipt round (<= 254), as in GP_FIRST, and is
+ * unique: u's frontier holds k in at most one round.  A line is fresh iff
+ * watch_arrival[a][k] == watch_first[s][k]; otherwise it is a duplicate and
+ * arrived later.  From the first-receipt matrix: watch_arrival[a][k] =
+ * first[u][k] + 1 iff first[u][k] != 255 and both u and v_s are up in round
+ * first[u][k]; a crashed sender's frontier is dropped, a send to a crashed
+ * watched peer arrives nowhere.  On a raw CSR parallel arcs are separate rows
+ * with equal contents and a self-loop is a row of duplicates.  Per watched
+ * peer, exactly: the cells != 255 count GP_LOAD_RECV[v_s], the fresh ones
+ * GP_FRESH_RECV[v_s] and per arc GP_LINK_FRESH[j], the messages with exactly
+ * one fresh arc GP_SOLE_RECV[v_s], and watch_first[s] is GP_FIRST's row.
+ *
+ * Scope: totals since gp_reset, readable between rounds (after R rounds the
+ * cells with value <= R; an injection of round R is not in it yet).  A context
+ * that runs a block of a message table (msg_word_base) holds its own messages'
+ * columns: the shards' arrays concatenate along k.  A vertex-partitioned
+ * context does not keep the record.  It is not in the checkpoint blob.
+ * Watching changes no other output; it makes the context keep the exact
+ * frontier rows, as gp_track_fresh does.
+ *
+ * gp_watch sets the list for the next gp_reset (count = 0: none; the record is
+ * then freed at that reset).  max_bytes bounds the two byte arrays, 0 meaning
+ * 1 GiB.  Checked at the call against the overlay then loaded: GP_ESTATE without
+ * one; GP_EINVAL for an id outside [0, n), a repeated id or count >
+ * GP_WATCH_MAX_PEERS; GP_ENOMEM when (A + K) * 64 W bytes, at the row width W
+ * the message table then has, exceed max_bytes -- gp_last_error names the size
+ * (gp_reset checks again if the table changed since).  A refused call leaves
+ * the previous list in force.  Loading another overlay drops the list.
+ * gp_watch_info reports the list in force for the current run (peers, arcs,
+ * bytes of the two arrays; 0s when none is); any pointer may be null.
+ *
+ * Reads: gp_read with the three kinds above (columns are the m real messages),
+ * and gp_read_watch_peer for one slot's [m] and [deg][m] (arrival_bytes must
+ * be deg * m), so that one hub's log does not cost a download of the whole
+ * record.  GP_ENOTRACK before the list has taken effect, and on a vertex-
+ * partitioned context; GP_ESTATE for a run restored from a checkpoint past
+ * round 0, until the next gp_reset; GP_EINVAL on a byte-count mismatch, a slot
+ * outside [0, K) or a null argument. */
+#define GP_WATCH_MAX_PEERS 65536
+int gp_watch(gp_ctx* ctx, int32_t count, const int32_t* verts, int64_t max_bytes);
+int gp_watch_info(gp_ctx* ctx, int32_t* count, int64_t* arcs, int64_t* bytes);
+int gp_read_watch_peer(gp_ctx* ctx, int32_t slot, void* first_row, void* arrival, int64_t arrival_bytes);
 
 /* Checkpoints (no reference counterpart -- the
  * reference's peers keep no state across restarts).  Taken between rounds:
