@@ -167,6 +167,8 @@ SIGNATURES = {
     "gp_watch": (ctypes.c_int, [_P, _I32, _P, _I64]),
     "gp_watch_info": (ctypes.c_int, [_P, _PI32, _PI64, _PI64]),
     "gp_read_watch_peer": (ctypes.c_int, [_P, _I32, _P, _P, _I64]),
+    "gp_link_loss": (ctypes.c_int, [_P, _I32, _D, _U64]),
+    "gp_link_loss_info": (ctypes.c_int, [_P, _PI32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]),
     "gp_checkpoint_size":(ctypes.c_int, [_P, _PI64]),
     "gp_checkpoint_save": (ctypes.c_int, [_P, _P, _I64]),
     "gp_checkpoint_load": (ctypes.c_int, [_P, _P, _I64]),

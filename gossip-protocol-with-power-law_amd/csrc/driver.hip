@@ -451,6 +451,7 @@ static RoundFacts round_facts(const Ctx* c) {
   f.lp_env = c->lp_env;
   f.can_park = !c->carry.park_failed;
   f.carry = c->carry;
+  f.lossy = c->loss_on;
   return f;
 }
 
@@ -474,12 +475,17 @@ static int launch_expand(Ctx* c) {
     f.can_list = false;
     p = plan_round(f);
   }
+  // (a lossy round reads every sender's exact frontier row: a state reallocated
+  // since the reset with the request withdrawn holds none)
+  if (p.pull.kernel == PULL_LOSSY && (!c->d_frx[0] || c->frx_rows < c->n_alloc))
+    return set_error(GP_ESTATE, "link loss is in force but the frontier rows are gone: gp_reset first");
   c->plan = p;
   c->acc_row = p.split ? (int32_t)f.acc_row : 0;
   if (alive_on(c))   // F_{r+1} is built by this round's receivers
     GP_HIP(hipMemsetAsync(c->d_alive + (size_t)(c->cur ^ 1) * c->words, 0, (size_t)c->words * 8, c->stream));
-  // a push's receivers and a list round's non-receivers start from fpop_next = 0
-  if ((p.mode_push && c->nloc() > 0) || p.ulist_read)
+  // a push's receivers and a list round's non-receivers start from fpop_next = 0;
+  // so does a lossy round, whose hubs are committed by the push's receiver side
+  if ((p.mode_push && c->nloc() > 0) || p.ulist_read || (p.pull.kernel == PULL_LOSSY && c->nloc() > 0))
     GP_HIP(hipMemsetAsync(c->d_fpop[c->cur ^ 1], 0, (size_t)c->nloc() * 4, c->stream));
   hipLaunchKernelGGL(k_mkbits, dim3(std::max(1, std::min(grid_for(c->n_alloc, BLOCK), c->cu_count * 8 * GS))),
                      dim3(BLOCK), 0, c->stream, c->d_fpop[c->cur], c->d_abits, c->n_alloc,
@@ -676,7 +682,7 @@ static int round_collect(Ctx* c, gp_round_stats* out) {
     out->atomics = h[S_ATOMICS];
     out->next_arcs = h[S_NEXT_ARCS];
     out->row_bytes = h[S_ROW_BYTES];
-    out->mode = c->plan.mode_push ? 1 : 0;
+    out->mode = c->plan.pull.kernel == PULL_LOSSY ? 2 : c->plan.mode_push ? 1 : 0;
     out->scan = c->plan.scan();
     out->kernel_ms = 0.0;
     if (!c->plan.mode_push && c->nloc() > 0) {

@@ -1061,6 +1061,9 @@ void launch_line_done(Ctx* c);                        // complete lines of the b
 template <int W> void launch_push_w(Ctx* c, ExpandArgs a);            // a push round
 template <int W> void launch_split_push_w(Ctx* c, const ExpandArgs& a);   // degree-split round: the push half
 template <int W> void launch_acc_clear_w(Ctx* c);                     // ... and its accumulator back to zero
+template <int W> void launch_apply_touched_w(Ctx* c, const ExpandArgs& a);   // the push's tail alone: touched list, receiver side
+// lossy.hip: an expansion round over lossy links (plan.pull.kernel == PULL_LOSSY)
+template <int W> void launch_expand_lossy_w(Ctx* c, const ExpandArgs& a);
 // hub.hip: the hub receivers of a pull round -- the chunks' partial rows (on
 // stream s: beside the round's main pull kernel), then the final rows (on the
 // engine stream, after both)

@@ -137,7 +137,7 @@ struct Ctx {
   // (carry.park_failed: it could not be)
   uint8_t* d_sp = nullptr;          // [n_alloc] slot of v's seen row (0xFF: none)
   uint8_t* d_ws = nullptr;          // [n_alloc] bit p: slot p written this run
-  u64* d_frx[2] = {nullptr, nullptr};     // exact frontier rows (track_msg_forwards; partitioned; spread curve; fresh deliveries)
+  u64* d_frx[2] = {nullptr, nullptr};     // exact frontier rows (track_msg_forwards; partitioned; spread curve; fresh deliveries; lossy links)
   int64_t frx_rows = 0;                   // rows d_frx covers (partitioned: the owned ones)
   // spread curve (curve.hip): [255][W * 64] first receipts per
   // receipt round and message over the owned vertices.  curve_want is what
@@ -249,9 +249,18 @@ struct Ctx {
   int32_t watch_words = 0;                // the row width the arrays were made for
   bool watch_alloc = false, watch_on = false, watch_valid = false;
   bool watch_want() const { return !h_watch_want.empty(); }
+  // lossy links (lossy.hip): every arc drops the lines of
+  // a round with probability p, by a draw of the ordered pair and the round.
+  // loss_want / loss_p_want / loss_seed_want are what gp_link_loss asked for,
+  // loss_alloc whether alloc_state sized the frontier rows for it, loss_on /
+  // loss_p / loss_seed the setting of the run since the last gp_reset
+  // (single-rank contexts only)
+  bool loss_want = false, loss_alloc = false, loss_on = false;
+  double loss_p_want = 0.0, loss_p = 0.0;
+  uint64_t loss_seed_want = 0, loss_seed = 0;
   bool holds_frx() const {
     return cfg.track_msg_forwards != 0 || local || curve_want || fresh_want || fresh_curve_want || link_want ||
-           delay_needs_rows() || mult_want || watch_want();
+           delay_needs_rows() || mult_want || watch_want() || loss_want;
   }
   uint32_t* d_fpop[2] = {nullptr, nullptr};    // [n_alloc]
   int cur = 0;
@@ -528,6 +537,8 @@ void watch_forget(Ctx* c);                     // a new overlay: the list's ids 
 int watch_count_round(Ctx* c);                 // after E_r: round r's arrivals at the watched peers, link by link
 void watch_restored(Ctx* c, int32_t round);    // gp_checkpoint_load: a run past round 0 lost its record
 int watch_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_WATCH_FIRST / GP_WATCH_ARRIVAL / GP_WATCH_PTR
+// lossy.hip
+int loss_reset(Ctx* c);                        // gp_reset: gp_link_loss takes effect, or the reset is refused
 // driver.hip: k_mkbits (and k_mksum) over fpop[cur], ahead of launch_expand
 int launch_activity_bits(Ctx* c, bool summary);
 // driver.hip: cnt[m] += the rows' bit m over rows [0, count) with guard[i] != 0 (the per-bit k_bitsum)

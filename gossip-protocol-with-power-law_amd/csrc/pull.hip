@@ -477,6 +477,10 @@ static int launch_expand_w(Ctx* c, ExpandArgs a) {
     launch_push_w<W>(c, a);
     return PULL_OK;
   }
+  if (c->plan.pull.kernel == PULL_LOSSY) {   // lossy links: a family of its own, none of the pull's passes (lossy.hip)
+    launch_expand_lossy_w<W>(c, a);
+    return PULL_OK;
+  }
   if (a.unfiltered && c->liveness_active) launch_park_w<W>(c);
   if (a.unfiltered) launch_fixup_rows_w<W>(c);
   // (k_line_done reads the rows as they are now: after the last round's k_hub_final, before the fork)
@@ -509,6 +513,7 @@ static int launch_expand_w(Ctx* c, ExpandArgs a) {
     case PULL_LIST: if (!launch_k_expand<W>(c, a, a.ulist_n, p.mode)) rc = PULL_NOT_BUILT; break;
     case PULL_RECEIVER: if (!launch_k_expand<W>(c, a, a.nloc, p.mode)) rc = PULL_NOT_BUILT; break;
     case PULL_RECORD: launch_expand_rec(c, a); break;
+    case PULL_LOSSY:   // (launched above)
     case PULL_NONE: break;
   }
   if (hubs) {   // join, then the hubs' rows

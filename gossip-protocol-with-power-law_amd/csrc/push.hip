@@ -384,6 +384,18 @@ void launch_push_w(Ctx* c, ExpandArgs a) {
                      a.orp, PUSH_CHUNK, c->d_active, c->d_big, c->d_stats, (const int64_t*)nullptr, 0);
   hipLaunchKernelGGL(k_push<W>, dim3(c->cu_count * 8 * GS), dim3(BLOCK), 0, s, a);
   hipLaunchKernelGGL(k_push_big<W>, dim3(c->cu_count * 4 * GS), dim3(BLOCK), 0, s, a);
+  launch_apply_touched_w<W>(c, a);
+}
+
+// The tail of a push on its own: the receivers whose tbits bit is set are
+// listed (the bitmap cleared) and committed from their accumulator rows, which
+// go back to all-zero.  A lossy round's hub items feed it (lossy.hip);
+// fpop_next starts zeroed, as in a push round
+template <int W>
+void launch_apply_touched_w(Ctx* c, const ExpandArgs& a) {
+  hipStream_t s = c->stream;
+  const int64_t nwords = (c->n_alloc + 63) / 64;
+  constexpr bool lanes = W <= GP_PUSH_LANES_MAXW;
   hipLaunchKernelGGL(k_touch_list, dim3(grid_for(nwords, BLOCK)), dim3(BLOCK), 0, s, c->d_tbits, nwords,
                      c->d_touched, c->d_stats);
   if (lanes)   // a wave per 64 touched receivers at a time, grid-stride
@@ -421,6 +433,13 @@ template void launch_push_w<8>(Ctx*, ExpandArgs);
 template void launch_push_w<16>(Ctx*, ExpandArgs);
 template void launch_push_w<32>(Ctx*, ExpandArgs);
 template void launch_push_w<64>(Ctx*, ExpandArgs);
+template void launch_apply_touched_w<1>(Ctx*, const ExpandArgs&);
+template void launch_apply_touched_w<2>(Ctx*, const ExpandArgs&);
+template void launch_apply_touched_w<4>(Ctx*, const ExpandArgs&);
+template void launch_apply_touched_w<8>(Ctx*, const ExpandArgs&);
+template void launch_apply_touched_w<16>(Ctx*, const ExpandArgs&);
+template void launch_apply_touched_w<32>(Ctx*, const ExpandArgs&);
+template void launch_apply_touched_w<64>(Ctx*, const ExpandArgs&);
 template void launch_split_push_w<1>(Ctx*, const ExpandArgs&);
 template void launch_split_push_w<2>(Ctx*, const ExpandArgs&);
 template void launch_split_push_w<4>(Ctx*, const ExpandArgs&);

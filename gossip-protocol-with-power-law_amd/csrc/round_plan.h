@@ -132,10 +132,13 @@ struct RoundFacts {
   // an allocation the plan asked for fails, and plans again)
   bool can_park = true, can_list = true;
   RoundCarry carry;
+  // lossy links: every arc may drop this round's lines
+  bool lossy = false;
 };
 
 // Which kernel pulls this round, and what its pre- and post-passes need to know.
-enum PullKernel { PULL_NONE, PULL_FLAT, PULL_LIST, PULL_RECEIVER, PULL_RECORD };
+enum PullKernel { PULL_NONE, PULL_FLAT, PULL_LIST, PULL_RECEIVER, PULL_RECORD,
+                  PULL_LOSSY /* k_expand_lossy: frontier rows through the per-arc draw (lossy.hip) */ };
 struct PullChoice {
   PullKernel kernel = PULL_NONE;
   int mode = 0;                   // k_expand's MODE (flat: SCAN_FILTERED / SCAN_UNFILTERED)
@@ -404,6 +407,16 @@ inline RoundPlan plan_pull(const RoundFacts& f, RoundPlan p) {
 
 // The round's plan.  No side effects: the same facts give the same plan.
 inline RoundPlan plan_round(const RoundFacts& f) {
+  // Lossy links: one kernel family and none of the switches,
+  // whatever the other facts say.  Push, early-exit target narrowing, the
+  // done-neighbour rules, aliases, line masks, records, the degree split,
+  // receiver lists, sating and parking each rest on "a neighbour's whole
+  // Message-List was sent to me", which a dropped line breaks
+  if (f.lossy) {
+    RoundPlan p;
+    p.pull.kernel = PULL_LOSSY;
+    return p;
+  }
   const gp_config& cfg = f.cfg;
   const double nm = (double)f.n * (double)f.m;
   const bool half_held = (double)f.held_bits * 2.0 >= nm;

@@ -350,7 +350,8 @@ static int alloc_state(Ctx* c) {
   // (the receipt delays and their distributions read the receivers' own new rows, delay.hip, delay_dist.hip -- unless every message starts in one round)
   const bool frx_record = c->cfg.track_msg_forwards || c->curve_want || c->fresh_want || c->fresh_curve_want ||
                           c->link_want || c->delay_needs_rows() || c->mult_want ||   // (and mult.hip)
-                          c->watch_want();                                            // (and the watched peers, watch.hip)
+                          c->watch_want() ||                                          // (and the watched peers, watch.hip)
+                          c->loss_want;                                               // (lossy links read them, lossy.hip)
   c->frx_rows = c->local ? c->nloc() : (frx_record ? c->n_alloc : 0);
   c->fresh_alloc = c->fresh_want;
   c->fresh_curve_alloc = c->fresh_curve_want;
@@ -358,6 +359,7 @@ static int alloc_state(Ctx* c) {
   c->delay_alloc = c->delay_needs_rows();
   c->mult_alloc = c->mult_want;
   c->watch_alloc = c->watch_want();
+  c->loss_alloc = c->loss_want;
   dfree(&c->d_slot[2]);   // (re)allocated at the first parking, for this W
   c->carry = RoundCarry{};   // (new buffers carry nothing over; parking may be tried again)
   // S[0] | S[1] | accumulator rows of the owned receivers, one allocation
@@ -898,13 +900,15 @@ int gp_spread_keys(gp_ctx* c, int32_t hops, int32_t m, const int32_t* origin, ui
 int gp_reset(gp_ctx* c) {
   if (!c) return set_error(GP_EINVAL, "null ctx");
   GP_HIP(hipSetDevice(c->device));
+  GP_TRY(loss_reset(c));   // (gp_link_loss takes effect here -- or refuses the reset, before anything changes)
   // (gp_track_curve, gp_track_fresh, gp_track_fresh_curve and gp_track_link_fresh take effect here: frontier
   // rows, the count buffer)
   if (!state_ready(c) || c->curve_alloc != c->curve_want || c->fresh_alloc != c->fresh_want ||
       c->fresh_curve_alloc != c->fresh_curve_want || c->link_alloc != c->link_want ||
       c->delay_alloc != c->delay_needs_rows() ||   // (gp_track_delay, gp_track_delay_dist: rows only for a table of several inject rounds)
       c->mult_alloc != c->mult_want ||             // (gp_track_mult)
-      c->watch_alloc != c->watch_want())           // (gp_watch)
+      c->watch_alloc != c->watch_want() ||         // (gp_watch)
+      c->loss_alloc != c->loss_want)               // (gp_link_loss)
     GP_TRY(alloc_state(c));
   if (!c->done_at_valid) {
     GP_TRY(compute_done_at(c, c->n_groups));

@@ -584,6 +584,26 @@ class GossipEngine:
         check(self._lib.gp_read_watch_peer(self._ctx, slot, _ptr(first), _ptr(arr), arr.nbytes))
         return first, arr
 
+    # -- lossy links (csrc/lossy.hip; helpers in loss.py) ----------------------
+    def link_loss(self, p, seed=0):
+        """gp_link_loss: from the next reset() on, every link drops the lines of
+        a round with probability p, by a draw of the ordered pair of peers and
+        the round (loss.arc_open is its numpy twin); link_loss(None) turns
+        loss off.  A dropped line is lost for good.  reset() refuses loss
+        together with a record that walks arcs (track_load, track_fresh,
+        track_fresh_curve, track_link_fresh, track_mult, watch) or a vertex
+        partition.  A p outside [0, 1] raises and leaves the request as it was."""
+        if p is None:
+            check(self._lib.gp_link_loss(self._ctx, 0, 0.0, 0))
+        else:
+            check(self._lib.gp_link_loss(self._ctx, 1, float(p), int(seed) & ((1 << 64) - 1)))
+
+    def link_loss_info(self):
+        """(on, p, seed) of the setting in force for the current run."""
+        on, p, seed = ctypes.c_int32(), ctypes.c_double(), ctypes.c_uint64()
+        check(self._lib.gp_link_loss_info(self._ctx, ctypes.byref(on), ctypes.byref(p), ctypes.byref(seed)))
+        return bool(on.value), p.value, seed.value
+
     def _nv(self):   # per-vertex reads: the owned slice of a partitioned context
         return self.nloc() if self.nranks > 1 else self.n
 

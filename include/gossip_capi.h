@@ -80,7 +80,8 @@ typedef struct gp_round_stats {
   uint64_t next_arcs;       /* out-degree sum of this round's receivers (direction)   */
   uint64_t row_bytes;       /* bytes of neighbour rows actually loaded (the pull skips
                                the words a receiver already completed, §3.4)         */
-  int32_t mode;             /* 0 = pull expansion, 1 = push expansion                 */
+  int32_t mode;             /* 0 = pull expansion, 1 = push expansion, 2 = expansion
+                               over lossy links (gp_link_loss below; scan is 0)      */
   int32_t scan;             /* pull arc check (bits 0-1 as a number): 0 = activity-
                                bitmap probe per arc, 1 = per-arc activity mask built
                                first, 2 = none, every in-neighbour row read (§3.4),
@@ -746,6 +747,50 @@ int gp_read_sole_bins(gp_ctx* ctx, uint64_t* out, int32_t bins);
 int gp_watch(gp_ctx* ctx, int32_t count, const int32_t* verts, int64_t max_bytes);
 int gp_watch_info(gp_ctx* ctx, int32_t* count, int64_t* arcs, int64_t* bytes);
 int gp_read_watch_peer(gp_ctx* ctx, int32_t slot, void* first_row, void* arrival, int64_t arrival_bytes);
+
+/* Lossy links (csrc/lossy.hip, csrc/link_loss.h).
+ * The flood of §2.2 delivers every line put on an arc.  With loss on, the line
+ * u puts on arc u -> v in round r arrives iff
+ *
+ *   draw(stream_key(seed, 0x200 + r), ((uint64_t)u << 32) | v) >= thresh
+ *
+ * with thresh = (uint64_t)ldexp(p, 64) for 0 < p < 1; p = 0 leaves every arc
+ * open, p = 1 closes every arc.  u and v are global vertex ids.  The draw
+ * belongs to the ordered pair and the round: it is the same for every message
+ * and every row width, independent for u -> v and v -> u, and parallel arcs of
+ * a raw CSR share it.  A vertex still sends a message only in the one round
+ * after its first receipt, so a line on a closed arc is lost for good: there
+ * is no retransmission.  `sends` and GP_FORWARDS stay the *attempted* sends;
+ * termination, injection, liveness and the digest (a function of the
+ * first-receipt matrix) are unchanged, and heartbeats are never dropped.  A
+ * message table run in blocks (msg_word_base) gives exactly the columns of
+ * the whole run, and no gp_config tuning field changes an output.  Coverage
+ * is NOT monotone in p for a fixed seed: receiving earlier moves a peer's one
+ * forwarding round onto another set of open arcs.
+ *
+ * gp_link_loss sets the request for the next gp_reset (on = 0: off; p and
+ * seed are then ignored beyond the range check).  GP_EINVAL for p < 0, p > 1
+ * or NaN: the previous request stays.  gp_link_loss_info reports the setting
+ * in force for the current run (any pointer may be null).
+ *
+ * gp_reset fails with GP_EINVAL, and changes nothing, when loss is requested
+ * together with a record that walks arcs -- gp_track_load, gp_track_fresh,
+ * gp_track_fresh_curve, gp_track_link_fresh, gp_track_mult, gp_watch (they
+ * would count closed arcs as deliveries; gp_last_error names the record) -- or
+ * in a vertex-partitioned context.  The records that read only the receivers'
+ * new rows stay exact: gp_track_curve, gp_track_delay, gp_track_delay_dist,
+ * track_first, track_digest, track_msg_forwards, coverage and forwards.
+ *
+ * Loss makes the context keep the exact frontier rows (as gp_track_fresh
+ * does): the lossy expansion reads them, not whole Message-Lists.  Its rounds
+ * report gp_round_stats.mode = 2 and scan = 0.
+ *
+ * Checkpoints: the blob does not record the loss setting.  The draw depends on
+ * the round number alone, so a blob loaded into a context with the same
+ * gp_link_loss setting (made before that context's gp_reset) continues
+ * bit-exactly; repeating the setting is the caller's job. */
+int gp_link_loss(gp_ctx* ctx, int32_t on, double p, uint64_t seed);
+int gp_link_loss_info(gp_ctx* ctx, int32_t* on, double* p, uint64_t* seed);
 
 /* Checkpoints (no reference counterpart -- the
  * reference's peers keep no state across restarts).  Taken between rounds:
