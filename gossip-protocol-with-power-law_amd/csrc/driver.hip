@@ -729,6 +729,25 @@ static int round_collect(Ctx* c, gp_round_stats* out) {
   return 0;
 }
 
+// dst[i] -= src[i], i < n
+__global__ void k_sub_u64(u64* __restrict__ dst, const u64* __restrict__ src, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] -= src[i];
+}
+
+// Forwards taken from the Message-Lists (no liveness, no track_msg_forwards)
+// count every holder of a message as a sender of it.  That is the run's sends
+// once it is quiescent; a run that stopped while its last round still made new
+// bits -- at the round limit, or because the caller stopped -- holds receivers
+// that have not sent yet.  pending: such receivers exist; unknown: and the
+// context keeps no frontier rows to take their share off again
+bool fwd_pending(const Ctx* c) {
+  return !c->liveness_active && !c->cfg.track_msg_forwards && c->round > 0 && c->prev_new_bits > 0;
+}
+bool forwards_unknown(const Ctx* c) {
+  return fwd_pending(c) && !(c->d_frx[0] && c->frx_rows >= c->nloc());
+}
+
 }  // namespace gp
 
 using namespace gp;
@@ -853,6 +872,22 @@ int gp_finalize_messages(gp_ctx* c) {
   // (bitcount.hip), forwards weighted by the static degree (= deg_live without liveness)
   if (c->done_at_valid && !finalize_by_rows()) GP_TRY(finalize_by_components(c, fwd_from_seen, cov, fwd_local));
   else GP_TRY(bitcount_messages(c, fwd_from_seen, cov, fwd_local));
+  // the last round's receivers have not sent their new bits: the next round's
+  // frontier x deg_live (what its track_msg_forwards pass would add) comes off
+  // again (gfwd is free until the copy below; GP_FORWARDS refuses the read
+  // where no frontier rows exist: forwards_unknown)
+  if (fwd_pending(c) && !forwards_unknown(c) && c->nloc() > 0) {
+    GP_HIP(hipMemsetAsync(gfwd, 0, M * 8, s));
+    BitsumArgs b{};
+    b.rows = c->d_frx[c->cur];
+    b.guard = c->d_fpop[c->cur];
+    b.weight = c->d_deg_live;
+    b.wsum = gfwd;
+    b.count = c->nloc();
+    GP_TRY(launch_bitsum(c, b, false, true));
+    hipLaunchKernelGGL(k_sub_u64, dim3(grid_for((int64_t)M, 256)), dim3(256), 0, s, fwd_local, gfwd, (int64_t)M);
+    GP_HIP(hipGetLastError());
+  }
   if (c->comm) {
     GP_RCCL(ncclGroupStart());
     GP_RCCL(ncclAllReduce(cov, gcov, M, ncclUint64, ncclSum, c->comm, s));
@@ -927,6 +962,9 @@ int gp_read(gp_ctx* c, int32_t what, void* host, int64_t bytes) {
       if (!run) return set_error(GP_ESTATE, "no run state");
       if (what == GP_FORWARDS && !c->msg_forwards_valid && c->liveness_active)
         return set_error(GP_ENOTRACK, "churn run without track_msg_forwards");
+      if (what == GP_FORWARDS && forwards_unknown(c))
+        return set_error(GP_ENOTRACK, "the run stopped before quiescence and keeps no frontier rows: its last "
+                                      "receivers' sends are not known (track_msg_forwards)");
       GP_TRY(need(M * 8));
       const size_t MM = (size_t)W * 64;
       const u64* src = c->d_msg_cov + (what == GP_COVERAGE ? 2 * MM : 3 * MM);

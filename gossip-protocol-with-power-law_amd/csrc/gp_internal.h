@@ -543,6 +543,10 @@ int loss_reset(Ctx* c);                        // gp_reset: gp_link_loss takes e
 int launch_activity_bits(Ctx* c, bool summary);
 // driver.hip: cnt[m] += the rows' bit m over rows [0, count) with guard[i] != 0 (the per-bit k_bitsum)
 int bitsum_count_rows(Ctx* c, const u64* rows, const uint32_t* guard, int64_t count, u64* cnt);
+// driver.hip: forwards read from the Message-Lists of a run that stopped before
+// quiescence, on a context without frontier rows: not kept (GP_ENOTRACK)
+bool fwd_pending(const Ctx* c);
+bool forwards_unknown(const Ctx* c);
 // partition.hip
 int localize(Ctx* c);                          // global overlay -> owned + ghost local CSR, boundary lists
 int set_extras(Ctx* c, const std::vector<int32_t>& origins_global);   // origins neither owned nor ghosts

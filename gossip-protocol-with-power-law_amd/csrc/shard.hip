@@ -320,7 +320,7 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
   hdr[H_N] = (u64)c->n; hdr[H_NNZ] = (u64)c->nnz; hdr[H_M] = (u64)c->m; hdr[H_WORDS] = (u64)c->words;
   hdr[H_WBASE] = (u64)c->cfg.msg_word_base; hdr[H_ROUNDS] = (u64)own;
   hdr[H_DIGEST] = c->cfg.track_digest ? 1 : 0;
-  hdr[H_FWD] = (!c->msg_forwards_valid && c->liveness_active) ? 0 : 1;
+  hdr[H_FWD] = ((!c->msg_forwards_valid && c->liveness_active) || forwards_unknown(c)) ? 0 : 1;
   hdr[H_CHURN] = (u64)c->cfg.churn; hdr[H_SEED] = c->cfg.churn_seed; hdr[H_PFAIL] = dbits(c->cfg.p_fail);
   hdr[H_DIRECTED] = (u64)c->directed;
   hdr[H_OK] = why.empty() ? 1 : 0;

@@ -362,6 +362,11 @@ class GossipEngine:
         return self._read(_lib.DIGEST, np.empty(self.nloc(), dtype=np.uint64))
 
     def finalize(self):
+        """gp_finalize_messages: coverage() and forwards() of the run so far.
+        After a run that stopped before quiescence (the 254-round limit, a
+        caller that stops early) the last round's receivers have not sent:
+        forwards() leaves their sends out, and raises GP_ENOTRACK on a context
+        that keeps neither frontier rows nor track_msg_forwards."""
         check(self._lib.gp_finalize_messages(self._ctx))
 
     def coverage(self):

@@ -274,7 +274,13 @@ int gp_run(gp_ctx* ctx, int32_t max_rounds, gp_round_stats* per_round, int32_t* 
  * different devices, no RCCL); the exchange is device-to-device copies and the
  * counters are summed into *out.  Used for partition-invariance checks on one GPU. */
 int gp_round_group(gp_ctx** ctxs, int32_t nctx, gp_round_stats* out);
-int gp_finalize_messages(gp_ctx* ctx);           /* per-message coverage/forwards    */
+/* Per-message coverage / forwards of the run so far.  Without liveness and
+ * track_msg_forwards the forwards come from the Message-Lists (every holder sent
+ * once to each link); in a run that stopped before quiescence -- the round
+ * limit, or a caller that stops -- the last round's receivers have not sent
+ * yet: their frontier rows come off again where the context keeps them, and
+ * where it keeps none GP_FORWARDS / GP_JOB_FORWARDS answer GP_ENOTRACK. */
+int gp_finalize_messages(gp_ctx* ctx);
 int gp_read(gp_ctx* ctx, int32_t what, void* host, int64_t bytes);
 int gp_reports(gp_ctx* ctx, gp_report* buf, int64_t cap, int64_t* n_out);
 int gp_synchronize(gp_ctx* ctx);
