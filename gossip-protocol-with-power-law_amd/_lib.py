@@ -172,7 +172,9 @@ SIGNATURES = {
     "gp_checkpoint_size":(ctypes.c_int, [_P, _PI64]),
     "gp_checkpoint_save": (ctypes.c_int, [_P, _P, _I64]),
     "gp_checkpoint_load": (ctypes.c_int, [_P, _P, _I64]),
+    "gp_selftest_lane_ops": (ctypes.c_int, [ctypes.c_int, _U64, ctypes.POINTER(ctypes.c_uint64)]),
 }
+LANE_SELFTEST_OPS = 32   # GP_LANE_SELFTEST_OPS
 
 ABI_VERSION = 18   # include/gossip_capi.h GP_ABI_VERSION (struct layouts below)
 _lib = None
@@ -209,6 +211,13 @@ def check(status):
         msg = load().gp_last_error()
         raise GossipError(status, msg.decode() if msg else "")
     return status
+
+
+def selftest_lane_ops(device=0, seed=1):
+    """gp_selftest_lane_ops: (mismatching lanes, result sums mod 2^64) per operation."""
+    out = (ctypes.c_uint64 * (2 * LANE_SELFTEST_OPS))()
+    check(load().gp_selftest_lane_ops(device, seed, out))
+    return list(out[:LANE_SELFTEST_OPS]), list(out[LANE_SELFTEST_OPS:])
 
 
 def device_count():

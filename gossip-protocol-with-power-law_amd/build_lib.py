@@ -61,6 +61,44 @@ def build_standin(force=False, verbose=True):
     return STANDIN_LIB
 
 
+LANE_OFF_UNITS = ("pull.hip", "hub.hip")   # the units GP_LANE_OPS changes (csrc/lane_ops.h)
+LANE_OFF_LIB = os.path.join(OUT_DIR, "libgossip_hip_lane_off.so")
+
+
+def build_lane_off(force=False, verbose=True):
+    """TEST build: the engine with GP_LANE_OPS=0 -- the pull family's cross-lane
+    reductions through LDS shuffles instead of csrc/lane_ops.h -- for the
+    on-against-off case of tests/test_gpu_lane_ops.py and for A/B runs.  Only
+    the units the knob changes are compiled again; the product library is not
+    touched."""
+    build(force=force, verbose=verbose)
+    deps = [os.path.join(CSRC, s) for s in list(LANE_OFF_UNITS) + HEADERS] + [INCLUDE, LIB, __file__]
+    if not force and not _stale(LANE_OFF_LIB, deps):
+        return LANE_OFF_LIB
+    objs, procs = [], []
+    for s in SOURCES:
+        stem = os.path.splitext(s)[0]
+        if s not in LANE_OFF_UNITS:
+            objs.append(os.path.join(OUT_DIR, stem + ".o"))
+            continue
+        obj = os.path.join(OUT_DIR, stem + ".lane_off.o")
+        objs.append(obj)
+        cmd = [_hipcc(), *FLAGS, "-DGP_LANE_OPS=0", "-c", os.path.join(CSRC, s), "-o", obj]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        procs.append(subprocess.Popen(cmd))
+    for p in procs:
+        if p.wait() != 0:
+            raise RuntimeError("hipcc failed")
+    tmp = LANE_OFF_LIB + ".tmp"
+    cmd = [_hipcc(), *FLAGS, "-shared", *objs, "-o", tmp, "-lrccl", "-pthread"]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    os.replace(tmp, LANE_OFF_LIB)
+    return LANE_OFF_LIB
+
+
 def build(force=False, verbose=True):
     os.makedirs(OUT_DIR, exist_ok=True)
     deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [INCLUDE, __file__]
@@ -89,3 +127,4 @@ def build(force=False, verbose=True):
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     build_standin(force="--force" in sys.argv)
+    build_lane_off(force="--force" in sys.argv)

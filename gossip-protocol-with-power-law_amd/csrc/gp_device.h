@@ -11,6 +11,7 @@
 #include <cstdint>
 
 #include "gp_internal.h"
+#include "lane_ops.h"
 #include "line_pack.h"
 #include "round_plan.h"
 
@@ -395,12 +396,36 @@ __device__ __forceinline__ u64 wave_sum_u64(u64 x) {
   for (int s = 32; s > 0; s >>= 1) x += __shfl_xor(x, s);
   return x;
 }
+// the wave reductions of the helpers the pull family shares with other units
+// (finish_row, commit_vertices, pair_finish): LO = in registers, wave-uniform
+// (lane_ops.h: every lane active); the other units' calls keep the LDS forms
+template <bool LO>
+__device__ __forceinline__ uint32_t wsum_u32(uint32_t x) {
+  if constexpr (LO && lane::ON) return lane::wave_sum_u32(x);
+  else return wave_sum_u32(x);
+}
+template <bool LO>
+__device__ __forceinline__ u64 wsum_u64(u64 x) {
+  if constexpr (LO && lane::ON) return lane::wave_sum_u64(x);
+  else return wave_sum_u64(x);
+}
+template <bool LO>
+__device__ __forceinline__ u64 wxor_u64(u64 x) {
+  if constexpr (LO && lane::ON) return lane::wave_xor_u64(x);
+  else return wave_xor_u64(x);
+}
 
 // OR-reduce the row slots of the wave: afterwards every lane holds the full
 // result for its lw column.
-template <int W>
+// LO: in registers (lane_ops.h; the pull family, W >= 8) -- every lane active
+template <int W, bool LO = false>
 __device__ __forceinline__ void reduce_slots(u64x2& acc) {
   constexpr int LPR = Geo<W>::LPR;
+  if constexpr (LO && lane::ON && W >= 8) {
+    acc.x = lane::slots_or<LPR>(acc.x);
+    acc.y = lane::slots_or<LPR>(acc.y);
+    return;
+  }
 #pragma unroll
   for (int s = LPR; s < 64; s <<= 1) {
     acc.x |= __shfl_xor(acc.x, s);
@@ -488,7 +513,7 @@ __device__ __forceinline__ bool gather_rows_n(const ExpandArgs& a, const int32_t
   bool live = true;   // this lane's words still miss messages
   if (ee) {
     u64x2 t = acc;
-    reduce_slots<W>(t);
+    reduce_slots<W, true>(t);
     const u64x2 miss = want & ~t;
     live = (miss.x | miss.y) != 0ull;
   }
@@ -509,7 +534,7 @@ __device__ __forceinline__ bool gather_rows_n(const ExpandArgs& a, const int32_t
     st.add(S_ROW_BYTES, pieces * (u64)(8 * Geo<W>::WPL));
     if (ee) {
       u64x2 t = acc;
-      reduce_slots<W>(t);
+      reduce_slots<W, true>(t);
       const u64x2 miss = want & ~t;
       live = (miss.x | miss.y) != 0ull;
       if (!__any(live)) return true;
@@ -571,7 +596,7 @@ __device__ __forceinline__ bool gather_rows_pack(const ExpandArgs& a, LDS& L, co
   static_assert(GP_PACK_RIF >= 1 && GP_PACK_RIF <= RIF, "the packed batch reuses the row batch's registers");
   const int lane = threadIdx.x & 63;
   int sh = 5, pp = lw;   // log2 of the lanes per row, and this lane's piece of it
-  reduce_slots<64>(acc);
+  reduce_slots<64, true>(acc);
   bool live;   // this lane's words still miss messages
   {
     const u64x2 miss = want & ~acc;
@@ -617,11 +642,16 @@ __device__ __forceinline__ bool gather_rows_pack(const ExpandArgs& a, LDS& L, co
     st.add(S_ROW_BYTES, pieces * 16ull);
     k0 += nq * rpi;
     // OR over the row slots, in place (lanes 2^sh apart hold the same piece)
+    if constexpr (lane::ON) {
+      acc.x = lane::slots_or_sh(acc.x, sh);
+      acc.y = lane::slots_or_sh(acc.y, sh);
+    } else {
 #pragma unroll
-    for (int s = 8; s < 64; s <<= 1) {
-      if (s >> sh) {
-        acc.x |= __shfl_xor(acc.x, s);
-        acc.y |= __shfl_xor(acc.y, s);
+      for (int s = 8; s < 64; s <<= 1) {
+        if (s >> sh) {
+          acc.x |= __shfl_xor(acc.x, s);
+          acc.y |= __shfl_xor(acc.y, s);
+        }
       }
     }
     const u64x2 miss = want & ~acc;
@@ -899,7 +929,9 @@ __device__ __forceinline__ void set_dense(u64* __restrict__ bm, int v) {
 // alias (DEFER, a.alias rounds): the receiver completes its component this
 // round (acc covers its early-exit target), so its new Message-List is its
 // component row: no row is written, the commit sets SLOT_CMASK
-template <int W, bool DEFER = false, bool CMLW = true, class LDS = WaveLds>
+// LO: the wave sums in registers (the pull family's calls; every lane is
+// active here: the early returns above them are wave-uniform)
+template <int W, bool DEFER = false, bool CMLW = true, bool LO = false, class LDS = WaveLds>
 __device__ __forceinline__ void finish_row(const ExpandArgs& a, int v, int64_t i, u64x2 acc, int lane,
                                            int g, int lw, WaveStats& st, LDS& L, bool have_sv,
                                            uint32_t sv_slot, int k = 0, bool alias = false) {
@@ -921,7 +953,7 @@ __device__ __forceinline__ void finish_row(const ExpandArgs& a, int v, int64_t i
     nw = acc & ~sv;
   }
   const uint32_t pc = (uint32_t)(__popcll(nw.x) + __popcll(nw.y));
-  const uint32_t tot = wave_sum_u32(pc);
+  const uint32_t tot = wsum_u32<LO>(pc);
   if (tot == 0) {
     if (!DEFER && lane == 0) a.fpop_next[v] = 0;
     return;
@@ -954,7 +986,7 @@ __device__ __forceinline__ void finish_row(const ExpandArgs& a, int v, int64_t i
       if (nw.x) t ^= digest_term((uint32_t)a.rr, (uint32_t)(a.wbase + lw * WPL), nw.x);
       if (WPL == 2 && nw.y) t ^= digest_term((uint32_t)a.rr, (uint32_t)(a.wbase + lw * WPL + 1), nw.y);
     }
-    t = wave_xor_u64(t);
+    t = wxor_u64<LO>(t);
     if constexpr (DEFER) {
       if (lane == 0) L.dig[k] = t;
     } else if (lane == 0) {
@@ -986,7 +1018,7 @@ __device__ __forceinline__ void finish_row(const ExpandArgs& a, int v, int64_t i
 
 // k_expand's commit of the deferred per-vertex words: lane k holds vertex
 // li = base + k, or in SCAN_LIST rounds the list's vertex (need: it was scanned)
-template <class LDS>
+template <bool LO = false, class LDS>
 __device__ __forceinline__ void commit_vertices(const ExpandArgs& a, LDS& L, int64_t li, bool need,
                                                 WaveStats& st) {
   wave_sync_lds();
@@ -1008,10 +1040,12 @@ __device__ __forceinline__ void commit_vertices(const ExpandArgs& a, LDS& L, int
       next_arcs = (u64)(uint32_t)max(a.deg_live[v], 0);
     }
   }
-  st.add(S_NEXT_ARCS, wave_sum_u64(next_arcs));
+  st.add(S_NEXT_ARCS, wsum_u64<LO>(next_arcs));
   if (a.lm_next) {   // line masks of the next round's senders, two vertices per byte (hubs: 0 here)
     const uint32_t nib = (need && L.tot[lane]) ? (uint32_t)(L.lmn[lane] & 0xF) : 0u;
-    const uint32_t hi = (uint32_t)__shfl_xor((int)nib, 1);
+    uint32_t hi;   // the odd neighbour's nibble
+    if constexpr (LO && lane::ON) hi = lane::dpp<lane::QUAD_XOR1>(nib);
+    else hi = (uint32_t)__shfl_xor((int)nib, 1);
     if (!(lane & 1) && li < a.nloc) a.lm_next[li >> 1] = (uint8_t)(nib | (hi << 4));
   }
   if constexpr (LDS::kCml) {   // the wave's 64 vertices are one word of the dense bitmap

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(HPBLOCK) void k_hub_partial(ExpandArgs a) {
             a, s0, min(hend, s0 + SUB), s_w[wib], lane, g, lw, acc, st, ee, want);
         if (ee) {
           u64x2 t = acc;
-          reduce_slots<W>(t);
+          reduce_slots<W, true>(t);
           const u64x2 miss = want & ~t;
           if (!__any((miss.x | miss.y) != 0ull)) {
             if (lane == 0 && a.hub_done)
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(HPBLOCK) void k_hub_partial(ExpandArgs a) {
           }
         }
       }
-      reduce_slots<W>(acc);
+      reduce_slots<W, true>(acc);
     }
     const bool nz = __any((acc.x | acc.y) != 0);
     if (nz && g == 0) store_piece<W>(a.hub_partial, it, lw, acc);
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(HBLOCK) void k_hub_final(ExpandArgs a) {
         }
         if (!__any((rem.x | rem.y) != 0ull) && lane == 0) a.state[v] |= ST_SATED;
       }
-      finish_row<W>(a, v, i, acc, lane, g, lw, st, s_w[wib], false, a.sp[v]);
+      finish_row<W, false, true, true>(a, v, i, acc, lane, g, lw, st, s_w[wib], false, a.sp[v]);
     }
   }
   alive_flush<W>(a, s_w[wib].alive, lane);

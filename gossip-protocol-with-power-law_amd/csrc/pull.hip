@@ -57,6 +57,11 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
   // done-probe variant behind them, which keeps its 70 VGPRs); the other
   // variants compile none of it
   constexpr bool LDONE = W == 64 && !ALIVE && !LIST && SCAN == SCAN_UNFILTERED;
+  // the serial loop's and the commit's cross-lane reductions in registers
+  // (lane_ops.h; GP_LANE_OPS).  Every variant: the line-mask one (C4 round 2),
+  // which reduces once per receiver, ran 0.1 ms slower with them and the run
+  // as fast with it left on LDS shuffles as without (profiles/r21_ab_lane_ops.txt)
+  constexpr bool LO = true;
   WaveStats st;
   ws_zero<EWAVES>(st);
   // the wave's block of 64 vertices: the blocks with a long non-hub in-list are
@@ -175,8 +180,8 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
         }
       }
     }
-    if constexpr ((MODE & 3) == SCAN_PRE) st.add(S_ARCS, (u64)wave_sum_u32(pre_arcs));
-    st.add(S_SENDS, wave_sum_u64(sends));
+    if constexpr ((MODE & 3) == SCAN_PRE) st.add(S_ARCS, (u64)wsum_u32<LO>(pre_arcs));
+    st.add(S_SENDS, wsum_u64<LO>(sends));
     st.add(S_ACTIVE, (u64)__popcll(__ballot(act)));
     st.add(S_VISITED, (u64)__popcll(__ballot(need)));
     L.tot[lane] = 0u;
@@ -378,7 +383,7 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
       } else {
         gather_scan<W, SCAN | (PACK ? SCAN_PACK : 0), DPROBE>(a, vb, ve, L, lane, g, lw, acc, st, ee, want, col0);
       }
-      reduce_slots<W>(acc);
+      reduce_slots<W, LO>(acc);
       if constexpr (ALIVE) {   // the round's gather covered every alive message v lacked: sated
         if (a.sate && ee && a.alive) {
           const u64x2 rem = want & ~acc;
@@ -402,11 +407,11 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
         const u64x2 rem = want & ~acc;
         full = !__any((rem.x | rem.y) != 0ull);
       }
-      finish_row<W, true, (MODE & SCAN_CML) != 0>(a, v, i, acc, lane, g, lw, st, L, ee || SEEN_EARLY, sv_slot, k,
-                                                  full);
+      finish_row<W, true, (MODE & SCAN_CML) != 0, LO>(a, v, i, acc, lane, g, lw, st, L, ee || SEEN_EARLY, sv_slot, k,
+                                                      full);
     }
     alive_flush<W>(a, L.alive, lane);
-    commit_vertices(a, L, vi, need, st);
+    commit_vertices<LO>(a, L, vi, need, st);
     if constexpr (ALIVE) {
       if (sat && ((sat >> lane) & 1ull)) a.state[a.vbegin + vi] |= ST_SATED;
     }
@@ -421,7 +426,8 @@ __global__ EXPAND_BOUNDS __attribute__((amdgpu_waves_per_eu(1))) void k_expand(E
         if (sm) {
           uint32_t p0 = 0;
           if (lane == 0) p0 = (uint32_t)atomicAdd(a.stats + S_ULIST, (u64)__popcll(sm));
-          p0 = (uint32_t)__shfl((int)p0, 0);
+          if constexpr (LO && lane::ON) p0 = (uint32_t)uniform((int)p0);   // (lane 0's: every lane is active)
+          else p0 = (uint32_t)__shfl((int)p0, 0);
           if (surv) a.ulist_next[p0 + lane_rank(sm)] = (int32_t)vi;
         }
       }

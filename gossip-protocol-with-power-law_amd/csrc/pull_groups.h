@@ -24,14 +24,20 @@ namespace gp {
 // kB < 0: half 1 idle) with its gathered OR acc and its seen row sv
 // (alias: both receivers complete their component -- done in-neighbours in an
 // a.alias round -- and commit SLOT_CMASK instead of a row, finish_row)
-template <int W, class LDS>
+// (LO: the half-wave reductions in registers, lane_ops.h -- k_expand's calls;
+// the record pull's keep the LDS shuffles)
+template <int W, bool LO = false, class LDS>
 __device__ __forceinline__ void pair_finish(const ExpandArgs& a, LDS& L, int h, int lw, bool on, int ks, int kB,
                                             int64_t i, int v, u64x2 acc, u64x2 sv, WaveStats& st,
                                             bool alias = false) {
   const u64x2 nw = acc & ~sv;
   uint32_t tot = (uint32_t)(__popcll(nw.x) + __popcll(nw.y));
+  if constexpr (LO && lane::ON) {
+    tot = lane::group_sum_u32<32>(tot);
+  } else {
 #pragma unroll
-  for (int o = 16; o > 0; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o);
+    for (int o = 16; o > 0; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o);
+  }
   u64 t = 0;
   bool dense = true;   // record of the new Message-List (record-writing rounds)
   if constexpr (LDS::kCml) {
@@ -63,8 +69,12 @@ __device__ __forceinline__ void pair_finish(const ExpandArgs& a, LDS& L, int h, 
       if (nw.y) t ^= digest_term((uint32_t)a.rr, (uint32_t)(a.wbase + 2 * lw + 1), nw.y);
     }
   }
+  if constexpr (LO && lane::ON) {
+    t = lane::group_xor_u64<32>(t);
+  } else {
 #pragma unroll
-  for (int o = 16; o > 0; o >>= 1) t ^= __shfl_xor(t, o);
+    for (int o = 16; o > 0; o >>= 1) t ^= __shfl_xor(t, o);
+  }
   uint32_t lmn = 0;   // lines of the new bits holding a nonzero word (lm_next; finish_row)
   if (a.lm_next) lmn = lines_of((uint32_t)(__ballot(on && (nw.x | nw.y) != 0ull) >> (32 * h)));
   if (lw == 0 && on && tot) {
@@ -136,7 +146,7 @@ __device__ __forceinline__ void pre_pairs(const ExpandArgs& a, LDS& L, u64 mp, i
     st.add(S_GATHERED, (u64)(npA + npB));
     st.add(S_ROW_BYTES, (u64)(npA + npB) * (u64)(8 * W));
     const u64x2 sv = pair_seen<W>(a, h, lw, on, kB, v, sv_slot, acc, st);
-    pair_finish<W>(a, L, h, lw, on, ks, kB, i, v, acc, sv, st);
+    pair_finish<W, true>(a, L, h, lw, on, ks, kB, i, v, acc, sv, st);
   }
 }
 
@@ -198,8 +208,12 @@ __device__ __forceinline__ void pre_quads(const ExpandArgs& a, LDS& L, u64 mq, i
     st.add(S_SEEN_READ, nsr);
     const u64x2 n0 = c0 & ~s0, n1 = c1 & ~s1;
     uint32_t tot = (uint32_t)(__popcll(n0.x) + __popcll(n0.y) + __popcll(n1.x) + __popcll(n1.y));
+    if constexpr (lane::ON) {   // (every lane active: the loop is wave-uniform)
+      tot = lane::group_sum_u32<16>(tot);
+    } else {
 #pragma unroll
-    for (int o = 8; o > 0; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o);
+      for (int o = 8; o > 0; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o);
+    }
     u64 t = 0;
     if (on && tot) {
       u64* out = a.slot[a.wslot] + (size_t)v * 64 + 4 * ql;
@@ -219,8 +233,12 @@ __device__ __forceinline__ void pre_quads(const ExpandArgs& a, LDS& L, u64 mq, i
         if (a.digest) t ^= digest_term((uint32_t)a.rr, (uint32_t)(a.wbase + 4 * ql + j), nw[j]);
       }
     }
+    if constexpr (lane::ON) {
+      t = lane::group_xor_u64<16>(t);
+    } else {
 #pragma unroll
-    for (int o = 8; o > 0; o >>= 1) t ^= __shfl_xor(t, o);
+      for (int o = 8; o > 0; o >>= 1) t ^= __shfl_xor(t, o);
+    }
     uint32_t lmn = 0;   // lines of the new bits holding a nonzero word (lm_next; pair_finish)
     if (a.lm_next) {
       const uint32_t bq = (uint32_t)((__ballot(on && ((n0.x | n0.y | n1.x | n1.y) != 0ull)) >> (16 * qd)) & 0xFFFFull);
@@ -333,7 +351,7 @@ __device__ __forceinline__ void dnb_pairs(const ExpandArgs& a, LDS& L, u64 mp, i
     const uint32_t sA = (uint32_t)__builtin_amdgcn_readlane((int)sv_slot, 0);
     const uint32_t sB = (uint32_t)__builtin_amdgcn_readlane((int)sv_slot, 32);
     st.add(S_SEEN_READ, (u64)((sA != SLOT_NONE ? 1 : 0) + (kB >= 0 && sB != SLOT_NONE ? 1 : 0)));
-    pair_finish<W>(a, L, h, lw, on, ks, kB, i, v, cm, sv, st, ALIAS && a.alias != 0);
+    pair_finish<W, true>(a, L, h, lw, on, ks, kB, i, v, cm, sv, st, ALIAS && a.alias != 0);
   }
 }
 
@@ -383,8 +401,12 @@ __device__ __forceinline__ void dnb_quads(const ExpandArgs& a, LDS& L, u64 mq, i
     }
     const u64x2 n0 = c0 & ~s0, n1 = c1 & ~s1;
     uint32_t tot = (uint32_t)(__popcll(n0.x) + __popcll(n0.y) + __popcll(n1.x) + __popcll(n1.y));
+    if constexpr (lane::ON) {   // (every lane active: the loop is wave-uniform)
+      tot = lane::group_sum_u32<16>(tot);
+    } else {
 #pragma unroll
-    for (int o = 8; o > 0; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o);
+      for (int o = 8; o > 0; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o);
+    }
     u64 t = 0;
     if (on && tot) {
       u64* out = a.slot[a.wslot] + (size_t)v * 64 + 4 * ql;
@@ -406,8 +428,12 @@ __device__ __forceinline__ void dnb_quads(const ExpandArgs& a, LDS& L, u64 mq, i
         if (a.digest) t ^= digest_term((uint32_t)a.rr, (uint32_t)(a.wbase + 4 * ql + j), nw[j]);
       }
     }
+    if constexpr (lane::ON) {
+      t = lane::group_xor_u64<16>(t);
+    } else {
 #pragma unroll
-    for (int o = 8; o > 0; o >>= 1) t ^= __shfl_xor(t, o);
+      for (int o = 8; o > 0; o >>= 1) t ^= __shfl_xor(t, o);
+    }
     if (ql == 0 && on && tot) {
       L.tot[ks] = tot;
       L.lmn[ks] = alias ? LMN_ALIAS : (uint8_t)0;   // (no line masks are written in early-exit rounds)
@@ -466,8 +492,12 @@ __device__ __forceinline__ void group_finish(const ExpandArgs& a, LDS& L, int lw
   constexpr int LG = Groups<W>::LG, NG = Groups<W>::NG;
   const u64x2 nw = acc & ~sv;
   uint32_t tot = (uint32_t)(__popcll(nw.x) + __popcll(nw.y));
+  if constexpr (lane::ON) {
+    tot = lane::group_sum_u32<LG>(tot);
+  } else {
 #pragma unroll
-  for (int o = LG / 2; o > 0; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o);
+    for (int o = LG / 2; o > 0; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o);
+  }
   u64 t = 0;
   if (on && tot) {
     alive_add<W>(a, L, lw, nw);
@@ -483,8 +513,12 @@ __device__ __forceinline__ void group_finish(const ExpandArgs& a, LDS& L, int lw
       if (nw.y) t ^= digest_term((uint32_t)a.rr, (uint32_t)(a.wbase + 2 * lw + 1), nw.y);
     }
   }
+  if constexpr (lane::ON) {
+    t = lane::group_xor_u64<LG>(t);
+  } else {
 #pragma unroll
-  for (int o = LG / 2; o > 0; o >>= 1) t ^= __shfl_xor(t, o);
+    for (int o = LG / 2; o > 0; o >>= 1) t ^= __shfl_xor(t, o);
+  }
   if (lw == 0 && on && tot) {
     L.tot[ks] = tot;
     L.lmn[ks] = 0;   // (line masks: W = 64 only)
@@ -764,7 +798,7 @@ __device__ __forceinline__ u64 gather_pairs(const ExpandArgs& a, LDS& L, u64 mp,
     }
     wave_sync_lds();   // (the next pair's column ids overwrite L.idx)
     const u64x2 sv = {L.seen[64 * h + 2 * lw], L.seen[64 * h + 2 * lw + 1]};
-    pair_finish<W>(a, L, h, lw, on, ks, kB, base + ks, v, acc, sv, st, ALIAS && a.alias != 0 && ee && full);
+    pair_finish<W, true>(a, L, h, lw, on, ks, kB, base + ks, v, acc, sv, st, ALIAS && a.alias != 0 && ee && full);
   }
   return sat;
 }

@@ -810,6 +810,24 @@ int gp_checkpoint_size(gp_ctx* ctx, int64_t* bytes);
 int gp_checkpoint_save(gp_ctx* ctx, void* host, int64_t bytes);
 int gp_checkpoint_load(gp_ctx* ctx, const void* host, int64_t bytes);
 
+/* Self-test of the in-register lane operations the pull kernels reduce with
+ * (csrc/lane_ops.h): sums, xors and ORs over the wave, over aligned groups of
+ * 4 / 8 / 16 / 32 lanes and over the row slots of every row width.  One small
+ * kernel on `device` evaluates each of the GP_LANE_SELFTEST_OPS operations
+ * beside its LDS-shuffle form on the same data: 4 waves of 68 patterns (all
+ * zero, all ones, each single lane set, the lane index, random words drawn
+ * from `seed`).  out_mismatches holds 2 * GP_LANE_SELFTEST_OPS words:
+ * [k] the lanes in which operation k's two forms differ (0 expected), and
+ * [GP_LANE_SELFTEST_OPS + k] the sum, modulo 2^64, of the in-register form's
+ * results over every pattern, wave and lane (for a check on the host).
+ * Operations: 5 * kind + size, kind = u32 sum, u64 sum, u64 xor, u64 OR,
+ * bool OR, size = groups of 4, 8, 16, 32 lanes, whole wave; then 25 .. 28 the
+ * slot OR of rows of 64, 32, 16, 8 words, and 29 .. 31 the packed gather's
+ * slot OR at 32, 16 and 8 lanes per slot.  Needs no context; no engine call
+ * uses it. */
+#define GP_LANE_SELFTEST_OPS 32
+int gp_selftest_lane_ops(int device, uint64_t seed, uint64_t* out_mismatches);
+
 #ifdef __cplusplus
 }
 #endif
