@@ -38,6 +38,8 @@ DELAY_DIST = 26                                       # per-peer delay distribut
 DELAY_DIST_BINS = 16                                  # its columns: delays 0 .. 14, 15 or more
 WATCH_FIRST, WATCH_ARRIVAL, WATCH_PTR = 27, 28, 29    # watched peers (gp_watch)
 WATCH_MAX_PEERS = 65536
+ARC_DELAY = 30                                        # delayed links (gp_link_delay): d(u, v) per in-CSR arc
+LINK_DELAY_MAX = 8
 # gp_shard_info transports
 XPORT_NONE, XPORT_RCCL, XPORT_HOST = 0, 1, 2
 
@@ -169,6 +171,8 @@ SIGNATURES = {
     "gp_read_watch_peer": (ctypes.c_int, [_P, _I32, _P, _P, _I64]),
     "gp_link_loss": (ctypes.c_int, [_P, _I32, _D, _U64]),
     "gp_link_loss_info": (ctypes.c_int, [_P, _PI32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]),
+    "gp_link_delay": (ctypes.c_int, [_P, _I32, _I32, _U64]),
+    "gp_link_delay_info": (ctypes.c_int, [_P, _PI32, _PI32, ctypes.POINTER(ctypes.c_uint64), _PI32]),
     "gp_checkpoint_size":(ctypes.c_int, [_P, _PI64]),
     "gp_checkpoint_save": (ctypes.c_int, [_P, _P, _I64]),
     "gp_checkpoint_load": (ctypes.c_int, [_P, _P, _I64]),

@@ -111,6 +111,8 @@ int gp_checkpoint_size(gp_ctx* c, int64_t* bytes) {
 int gp_checkpoint_save(gp_ctx* c, void* host, int64_t bytes) {
   if (!c || !host) return set_error(GP_EINVAL, "null argument");
   if (!run_state(c)) return set_error(GP_ESTATE, "no run state (gp_reset first)");
+  if (c->lag_on && c->lag_dmax > 1)   // (delayed.hip: the blob holds one round's frontier rows)
+    return set_error(GP_ESTATE, "link delay with dmax > 1 is in force: the lines in flight are not in a checkpoint");
   const int64_t nrep = saved_reports(c);
   if (bytes != blob_bytes(c, nrep))
     return set_error(GP_EINVAL, "bytes mismatch: expected " + std::to_string(blob_bytes(c, nrep)));
@@ -187,6 +189,8 @@ int gp_checkpoint_load(gp_ctx* c, const void* host, int64_t bytes) {
     return set_error(GP_EINVAL, "checkpoint holds more reports than report_capacity");
   if (bytes != blob_bytes(c, h.saved_reports))
     return set_error(GP_EINVAL, "bytes mismatch: expected " + std::to_string(blob_bytes(c, h.saved_reports)));
+  if (c->lag_want && c->lag_dmax_want > 1)   // (the reset below would put the request in force)
+    return set_error(GP_ESTATE, "link delay with dmax > 1 is requested: a checkpoint holds no lines in flight");
   GP_TRY(gp_reset(c));   // accepted: clear the run state, then fill it from the blob
   GP_HIP(hipSetDevice(c->device));
   const uint8_t* in = static_cast<const uint8_t*>(host);

@@ -451,7 +451,7 @@ static RoundFacts round_facts(const Ctx* c) {
   f.lp_env = c->lp_env;
   f.can_park = !c->carry.park_failed;
   f.carry = c->carry;
-  f.lossy = c->loss_on;
+  f.lossy = c->loss_on || c->lag_on;   // (delayed links read frontier rows through the same plan, delayed.hip)
   return f;
 }
 
@@ -548,11 +548,13 @@ int bitsum_count_rows(Ctx* c, const u64* rows, const uint32_t* guard, int64_t co
 static int round_launch(Ctx* c) {
   if (!state_ready(c) || c->words <= 0) return set_error(GP_ESTATE, "gp_set_messages + gp_reset first");
   if (c->round > 253) return set_error(GP_ESTATE, "round limit (254) reached");
+  GP_TRY(lag_check_round(c));   // (delayed links: before anything of the round is enqueued)
   GP_HIP(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   u64* stats = c->d_stats;
   u64* partial = c->d_stats + 64;
   const int r = c->round;
+  lag_rotate(c);   // (delayed links: d_frx[cur] / d_frx[cur ^ 1] are the ring's slots of rounds r and r + 1)
   GP_HIP(hipMemsetAsync(stats, 0, 64 * sizeof(u64), s));
   GP_HIP(hipEventRecord(c->ev[0], s));
   if (c->liveness_active) {
@@ -711,6 +713,7 @@ static int round_collect(Ctx* c, gp_round_stats* out) {
   c->prev_new_bits = h[S_NEW_BITS];
   c->prev_receivers = h[S_RECEIVERS];
   c->held_bits += h[S_INJECTED] + h[S_NEW_BITS];
+  c->lag_hist = (c->lag_hist << 1) | (h[S_ACTIVE] ? 1u : 0u);   // (delayed links: lag_in_flight)
   {   // what this round hands to the next one
     const RoundPlan& p = c->plan;
     RoundCarry& k = c->carry;
@@ -778,6 +781,7 @@ int gp_round(gp_ctx* c, gp_round_stats* out) {
     return set_error(GP_ESTATE, "a partitioned context exchanges over RCCL (gp_comm_init) or in gp_round_group");
   // (message-shard job, shard.hip: the history check and its growth come
   // first, so that no error of theirs can leave a round half applied)
+  GP_TRY(lag_check_round(c));   // (delayed links are refused in a shard job: before its history moves)
   if (c->jnranks > 0) GP_TRY(shard_prepare_round(c));
   GP_TRY(round_launch(c));
   GP_TRY(round_exchange_rccl(c));
@@ -845,7 +849,8 @@ int gp_run(gp_ctx* c, int32_t max_rounds, gp_round_stats* per_round, int32_t* ro
     GP_TRY(gp_round(c, &st));
     if (per_round) per_round[k] = st;
     ++done;
-    if (st.new_bits == 0 && st.round >= c->last_inject_round) break;
+    // (delayed links: and nothing in flight -- no sender in the last dmax - 1 rounds)
+    if (st.new_bits == 0 && st.round >= c->last_inject_round && lag_in_flight(c) == 0) break;
   }
   if (rounds_out) *rounds_out = done;
   return 0;
@@ -1059,6 +1064,8 @@ int gp_read(gp_ctx* c, int32_t what, void* host, int64_t bytes) {
     case GP_WATCH_ARRIVAL:
     case GP_WATCH_PTR:   // watched peers (watch.hip)
       return watch_read(c, what, host, bytes);
+    case GP_ARC_DELAY:   // delayed links (delayed.hip)
+      return lag_read(c, host, bytes);
     case GP_SEENPOP:
       if (!run) return set_error(GP_ESTATE, "no run state");
       GP_TRY(need(nl * 4));

@@ -258,9 +258,28 @@ struct Ctx {
   bool loss_want = false, loss_alloc = false, loss_on = false;
   double loss_p_want = 0.0, loss_p = 0.0;
   uint64_t loss_seed_want = 0, loss_seed = 0;
+  // delayed links (delayed.hip): the link between u and
+  // v takes d(u, v) in [1, dmax] rounds, fixed for the run (link_delay.h).
+  // lag_want / lag_dmax_want / lag_seed_want are what gp_link_delay asked for,
+  // lag_alloc whether alloc_state sized the frontier rows for it, lag_on /
+  // lag_dmax / lag_seed the setting of the run since the last gp_reset
+  // (single-rank contexts only).  While the ring is in force (lag_ring > 0) it
+  // owns every frontier-row buffer: d_lag_frx[0] and [1] are alloc_state's two,
+  // the rest its own, and d_frx[cur] / d_frx[cur ^ 1] are rotated through them
+  // each round (lag_rotate); lag_release hands the first two back to d_frx
+  // before anything frees or reallocates them
+  bool lag_want = false, lag_alloc = false, lag_on = false;
+  int32_t lag_dmax_want = 1, lag_dmax = 1;
+  uint64_t lag_seed_want = 0, lag_seed = 0;
+  uint32_t lag_hist = 0;               // bit k: round - 1 - k of this run had a sender (lag_in_flight)
+  int32_t lag_ring = 0;                   // buffers of the ring in force: lag_dmax + 1 (0: no ring)
+  u64* d_lag_frx[9] = {};                 // [lag_ring] frontier rows of round s live in slot s % lag_ring
+  u64* d_lag_bits = nullptr;              // [lag_dmax + 1][lag_nw] k_mkbits' bitmap of round s in row s % lag_dmax; last row: their OR
+  int64_t lag_nw = 0;                     // words per bitmap row
+  uint8_t* d_lag_arc = nullptr;           // [nnz] d(u, v) per arc of the in-CSR
   bool holds_frx() const {
     return cfg.track_msg_forwards != 0 || local || curve_want || fresh_want || fresh_curve_want || link_want ||
-           delay_needs_rows() || mult_want || watch_want() || loss_want;
+           delay_needs_rows() || mult_want || watch_want() || loss_want || lag_want;
   }
   uint32_t* d_fpop[2] = {nullptr, nullptr};    // [n_alloc]
   int cur = 0;
@@ -539,6 +558,15 @@ void watch_restored(Ctx* c, int32_t round);    // gp_checkpoint_load: a run past
 int watch_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_WATCH_FIRST / GP_WATCH_ARRIVAL / GP_WATCH_PTR
 // lossy.hip
 int loss_reset(Ctx* c);                        // gp_reset: gp_link_loss takes effect, or the reset is refused
+// delayed.hip
+int lag_reset(Ctx* c);                         // gp_reset, before anything changes: gp_link_delay's request can take effect, or the reset is refused
+int lag_prepare(Ctx* c);                       // gp_reset, with the run state in place: it takes effect; the ring, the bitmaps, the arc delays
+void lag_release(Ctx* c);                      // d_frx owns its two buffers again; the ring's own are freed
+bool lag_ready(const Ctx* c);                  // the ring in force matches the setting in force
+void lag_rotate(Ctx* c);                       // round r: d_frx[cur] / d_frx[cur ^ 1] = the ring's slots of rounds r / r + 1
+int lag_check_round(const Ctx* c);             // before a round: GP_ESTATE when delay is in force without its ring, or in a shard job
+int32_t lag_in_flight(const Ctx* c);           // past send rounds whose lines may still arrive (0: delay off, or none)
+int lag_read(Ctx* c, void* host, int64_t bytes);   // GP_ARC_DELAY
 // driver.hip: k_mkbits (and k_mksum) over fpop[cur], ahead of launch_expand
 int launch_activity_bits(Ctx* c, bool summary);
 // driver.hip: cnt[m] += the rows' bit m over rows [0, count) with guard[i] != 0 (the per-bit k_bitsum)

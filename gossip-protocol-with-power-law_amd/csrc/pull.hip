@@ -484,7 +484,8 @@ static int launch_expand_w(Ctx* c, ExpandArgs a) {
     return PULL_OK;
   }
   if (c->plan.pull.kernel == PULL_LOSSY) {   // lossy links: a family of its own, none of the pull's passes (lossy.hip)
-    launch_expand_lossy_w<W>(c, a);
+    if (c->lag_on) launch_expand_delayed_w<W>(c, a);   // delayed links, dmax = 1 included (delayed.hip)
+    else launch_expand_lossy_w<W>(c, a);
     return PULL_OK;
   }
   if (a.unfiltered && c->liveness_active) launch_park_w<W>(c);

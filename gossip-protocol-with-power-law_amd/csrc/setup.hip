@@ -238,6 +238,7 @@ static void free_rows(Ctx* c) {
 }
 
 static void free_state(Ctx* c) {
+  lag_release(c);   // (delayed links: d_frx owns its two buffers again)
   dfree(&c->d_slot[2]);
   free_rows(c);
   for (int k = 0; k < 2; ++k) {
@@ -351,7 +352,9 @@ static int alloc_state(Ctx* c) {
   const bool frx_record = c->cfg.track_msg_forwards || c->curve_want || c->fresh_want || c->fresh_curve_want ||
                           c->link_want || c->delay_needs_rows() || c->mult_want ||   // (and mult.hip)
                           c->watch_want() ||                                          // (and the watched peers, watch.hip)
-                          c->loss_want;                                               // (lossy links read them, lossy.hip)
+                          c->loss_want ||                                             // (lossy links read them, lossy.hip)
+                          c->lag_want;                                                // (and delayed links, delayed.hip)
+  lag_release(c);   // (before d_frx is reallocated: a ring may have rotated its pointers)
   c->frx_rows = c->local ? c->nloc() : (frx_record ? c->n_alloc : 0);
   c->fresh_alloc = c->fresh_want;
   c->fresh_curve_alloc = c->fresh_curve_want;
@@ -360,6 +363,7 @@ static int alloc_state(Ctx* c) {
   c->mult_alloc = c->mult_want;
   c->watch_alloc = c->watch_want();
   c->loss_alloc = c->loss_want;
+  c->lag_alloc = c->lag_want;
   dfree(&c->d_slot[2]);   // (re)allocated at the first parking, for this W
   c->carry = RoundCarry{};   // (new buffers carry nothing over; parking may be tried again)
   // S[0] | S[1] | accumulator rows of the owned receivers, one allocation
@@ -609,6 +613,7 @@ void gp_destroy(gp_ctx* c) {
   if (c->side) (void)hipStreamSynchronize(c->side);
   if (c->comm) (void)ncclCommDestroy(c->comm);
   shard_free(c);
+  lag_release(c);
   dfree(&c->d_row_ptr); dfree(&c->d_col); dfree(&c->d_out_row_ptr); dfree(&c->d_out_col);
   dfree(&c->d_deg_out); dfree(&c->d_comp); dfree(&c->d_abits); dfree(&c->d_dbits); dfree(&c->d_lm); dfree(&c->d_lmw[0]); dfree(&c->d_lmw[1]); dfree(&c->d_sbits); dfree(&c->d_amask); dfree(&c->d_cml[0]); dfree(&c->d_cml[1]); dfree(&c->d_cmk[0]); dfree(&c->d_cmk[1]); dfree(&c->d_done_at);
   dfree(&c->d_done_at0); dfree(&c->d_cmask0); dfree(&c->d_lostcnt); dfree(&c->d_alive);
@@ -900,6 +905,7 @@ int gp_spread_keys(gp_ctx* c, int32_t hops, int32_t m, const int32_t* origin, ui
 int gp_reset(gp_ctx* c) {
   if (!c) return set_error(GP_EINVAL, "null ctx");
   GP_HIP(hipSetDevice(c->device));
+  GP_TRY(lag_reset(c));    // (gp_link_delay may refuse the reset, before anything changes; lag_prepare below applies it)
   GP_TRY(loss_reset(c));   // (gp_link_loss takes effect here -- or refuses the reset, before anything changes)
   // (gp_track_curve, gp_track_fresh, gp_track_fresh_curve and gp_track_link_fresh take effect here: frontier
   // rows, the count buffer)
@@ -908,7 +914,8 @@ int gp_reset(gp_ctx* c) {
       c->delay_alloc != c->delay_needs_rows() ||   // (gp_track_delay, gp_track_delay_dist: rows only for a table of several inject rounds)
       c->mult_alloc != c->mult_want ||             // (gp_track_mult)
       c->watch_alloc != c->watch_want() ||         // (gp_watch)
-      c->loss_alloc != c->loss_want)               // (gp_link_loss)
+      c->loss_alloc != c->loss_want ||             // (gp_link_loss)
+      c->lag_alloc != c->lag_want)                 // (gp_link_delay)
     GP_TRY(alloc_state(c));
   if (!c->done_at_valid) {
     GP_TRY(compute_done_at(c, c->n_groups));
@@ -963,6 +970,7 @@ int gp_reset(gp_ctx* c) {
   GP_TRY(delay_dist_reset(c));    // (and gp_track_delay_dist)
   GP_TRY(mult_reset(c));          // (and gp_track_mult)
   GP_TRY(watch_reset(c));         // (and gp_watch)
+  GP_TRY(lag_prepare(c));         // (and gp_link_delay: the ring of frontier rows, the arc delays)
   GP_HIP(hipStreamSynchronize(s));
   return 0;
 }

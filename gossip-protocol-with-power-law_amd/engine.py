@@ -609,6 +609,38 @@ class GossipEngine:
         check(self._lib.gp_link_loss_info(self._ctx, ctypes.byref(on), ctypes.byref(p), ctypes.byref(seed)))
         return bool(on.value), p.value, seed.value
 
+    # -- delayed links (csrc/delayed.hip; helpers in lag.py) -------------------
+    def link_delay(self, dmax, seed=0):
+        """gp_link_delay: from the next reset() on, the link between peers u
+        and v takes d(u, v) in [1, dmax] rounds, dmax <= 8, by a draw of the
+        unordered pair (lag.arc_delay is its numpy twin); link_delay(None)
+        turns delay off, link_delay(1) is the flood through the delayed
+        kernels.  Rounds without a new bit occur while lines are in flight:
+        run() stops by the delayed rule, a loop over round() reads
+        link_delay_info()[3].  reset() refuses delay together with a record
+        that walks arcs (track_load, track_fresh, track_fresh_curve,
+        track_link_fresh, track_mult, watch), a vertex partition or a
+        message-shard job; checkpoint() refuses with dmax > 1 in force.  A dmax
+        outside [1, 8] raises and leaves the request as it was."""
+        if dmax is None:
+            check(self._lib.gp_link_delay(self._ctx, 0, 1, 0))
+        else:
+            check(self._lib.gp_link_delay(self._ctx, 1, int(dmax), int(seed) & ((1 << 64) - 1)))
+
+    def link_delay_info(self):
+        """(on, dmax, seed, in_flight) of the setting in force for the current
+        run; in_flight counts the past rounds whose lines may still arrive (0:
+        nothing is under way)."""
+        on, dmax, seed, fl = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_uint64(), ctypes.c_int32()
+        check(self._lib.gp_link_delay_info(self._ctx, ctypes.byref(on), ctypes.byref(dmax), ctypes.byref(seed),
+                                           ctypes.byref(fl)))
+        return bool(on.value), dmax.value, seed.value, fl.value
+
+    def arc_delays(self):
+        """u8 [nnz]: d(u, v) of arc j of graph() (sender col[j], receiver the
+        row of j) while delay is in force (lag.arc_delays is its numpy twin)."""
+        return self._read(_lib.ARC_DELAY, np.empty(self.info()[1], dtype=np.uint8))
+
     def _nv(self):   # per-vertex reads: the owned slice of a partitioned context
         return self.nloc() if self.nranks > 1 else self.n
 

@@ -81,7 +81,8 @@ typedef struct gp_round_stats {
   uint64_t row_bytes;       /* bytes of neighbour rows actually loaded (the pull skips
                                the words a receiver already completed, §3.4)         */
   int32_t mode;             /* 0 = pull expansion, 1 = push expansion, 2 = expansion
-                               over lossy links (gp_link_loss below; scan is 0)      */
+                               over lossy or delayed links (gp_link_loss, gp_link_delay
+                               below; scan is 0)                                      */
   int32_t scan;             /* pull arc check (bits 0-1 as a number): 0 = activity-
                                bitmap probe per arc, 1 = per-arc activity mask built
                                first, 2 = none, every in-neighbour row read (§3.4),
@@ -209,7 +210,9 @@ typedef enum gp_what {
   /* watched peers (gp_watch below) */
   GP_WATCH_FIRST = 27,   /* u8  [K][m]  first-receipt rows of the watched peers, 255 = never */
   GP_WATCH_ARRIVAL = 28, /* u8  [A][m]  receipt round per watched in-arc and message, 255 = never */
-  GP_WATCH_PTR = 29      /* i64 [K+1]   first watched arc of every slot                      */
+  GP_WATCH_PTR = 29,     /* i64 [K+1]   first watched arc of every slot                      */
+  /* delayed links (gp_link_delay below) */
+  GP_ARC_DELAY = 30      /* u8  [nnz]   d(u, v) of arc j of the in-CSR, in GP_ROW_PTR / GP_COL order */
 } gp_what;
 
 int gp_abi_version(void);
@@ -797,6 +800,61 @@ int gp_read_watch_peer(gp_ctx* ctx, int32_t slot, void* first_row, void* arrival
  * bit-exactly; repeating the setting is the caller's job. */
 int gp_link_loss(gp_ctx* ctx, int32_t on, double p, uint64_t seed);
 int gp_link_loss_info(gp_ctx* ctx, int32_t* on, double* p, uint64_t* seed);
+
+/* Delayed links (csrc/delayed.hip, csrc/link_delay.h; DESIGN.md §2.2, §2.6,
+ * §3.19).  The flood of §2.2 crosses every link in one round.  With delay on,
+ * the link between u and v takes
+ *
+ *   d(u, v) = 1 + below(draw(stream_key(seed, 0x300),
+ *                            ((uint64_t)min(u, v) << 32) | max(u, v)), dmax)
+ *
+ * rounds, dmax in [1, 8], u and v global vertex ids: the line u sends in round
+ * s (it still sends a message only in the round after its first receipt) has
+ * receipt round s + d(u, v).  The delay belongs to the unordered pair and is
+ * fixed for the run: a link is as slow one way as the other, the same for every
+ * message and row width, and parallel arcs of a raw CSR share it.  dmax = 1 is
+ * the flood, bit for bit.  `sends`, `active` and GP_FORWARDS count attempted
+ * sends in the send round.  A line already sent still arrives if its sender
+ * crashes later; a receiver down in the arrival round loses it for good;
+ * heartbeats are not delayed.  With gp_link_loss as well, the line sent in
+ * round s arrives iff arc u -> v was open in round s.  Without loss and
+ * liveness first[v][k] = inject[k] + the shortest-path distance from origin[k]
+ * to v under d, and coverage equals the flood's.  A message table run in blocks
+ * (msg_word_base) gives the columns of the whole run, and no gp_config tuning
+ * field changes an output.
+ *
+ * Termination: a run is over after the first round r >= the last inject round
+ * with new_bits = 0 and no sender in any round of [r + 2 - dmax, r] -- nothing
+ * is in flight.  gp_run stops by this rule; a caller stepping gp_round reads
+ * in_flight from gp_link_delay_info: the number of rounds s in
+ * [round + 1 - dmax, round - 1] with active > 0 (0 with delay off).  Rounds
+ * with new_bits = 0 occur before the end.
+ *
+ * gp_link_delay sets the request for the next gp_reset (on = 0: off; seed is
+ * then ignored).  GP_EINVAL for dmax outside [1, 8], also with on = 0: the
+ * previous request stays.  gp_link_delay_info reports the setting in force for
+ * the current run (any pointer may be null).  GP_ARC_DELAY reads d per arc of
+ * the in-CSR while delay is in force (GP_ENOTRACK otherwise).
+ *
+ * gp_reset fails with GP_EINVAL, and changes nothing, when delay is requested
+ * together with gp_track_load, gp_track_fresh, gp_track_fresh_curve,
+ * gp_track_link_fresh, gp_track_mult or gp_watch (they take every line to
+ * arrive in its send round; gp_last_error names the record), in a
+ * vertex-partitioned context, in a message-shard job (gp_shard_*), or on more
+ * than 2^28 vertices; with GP_ENOMEM when the ring of dmax + 1 frontier-row
+ * buffers cannot be allocated (no delay is then in force, gp_link_delay_info
+ * says so, and the context stays usable: the request stands for the next
+ * gp_reset, or is withdrawn).  A shard transport joined after the reset of a
+ * delayed run makes every further gp_round fail with GP_ESTATE, before
+ * anything of the round is enqueued.  gp_track_curve, gp_track_delay, gp_track_delay_dist,
+ * track_first, track_digest, track_msg_forwards, coverage and forwards stay
+ * exact.  Delayed rounds report gp_round_stats.mode = 2 and scan = 0.
+ *
+ * Checkpoints: the lines in flight are not in the blob.  gp_checkpoint_save
+ * with dmax > 1 in force, and gp_checkpoint_load with dmax > 1 requested, fail
+ * with GP_ESTATE; dmax = 1 behaves as gp_link_loss does. */
+int gp_link_delay(gp_ctx* ctx, int32_t on, int32_t dmax, uint64_t seed);
+int gp_link_delay_info(gp_ctx* ctx, int32_t* on, int32_t* dmax, uint64_t* seed, int32_t* in_flight);
 
 /* Checkpoints (no reference counterpart -- the
  * reference's peers keep no state across restarts).  Taken between rounds:
