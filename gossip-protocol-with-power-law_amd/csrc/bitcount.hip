@@ -437,16 +437,7 @@ int bitcount_messages(Ctx* c, bool weighted, u64* cov, u64* fwd) {
   a.keys = weighted ? c->d_bc_keys : nullptr;
   a.count = n;
   a.part = c->d_bc_part;
-  switch (W) {
-    case 1: launch_bitcount_w<1>(c, a, weighted, nblocks); break;
-    case 2: launch_bitcount_w<2>(c, a, weighted, nblocks); break;
-    case 4: launch_bitcount_w<4>(c, a, weighted, nblocks); break;
-    case 8: launch_bitcount_w<8>(c, a, weighted, nblocks); break;
-    case 16: launch_bitcount_w<16>(c, a, weighted, nblocks); break;
-    case 32: launch_bitcount_w<32>(c, a, weighted, nblocks); break;
-    case 64: launch_bitcount_w<64>(c, a, weighted, nblocks); break;
-    default: return set_error(GP_EINVAL, "unsupported word count");
-  }
+  GP_TRY(with_words(W, [&](auto w) { launch_bitcount_w<w()>(c, a, weighted, nblocks); }));
   GP_HIP(hipMemsetAsync(cov, 0, (size_t)M * 8, c->stream));
   if (weighted) GP_HIP(hipMemsetAsync(fwd, 0, (size_t)M * 8, c->stream));
   const int slices = std::max(1, std::min(nblocks / 16, 64));
@@ -618,20 +609,10 @@ int finalize_by_components(Ctx* c, bool weighted, u64* cov, u64* fwd) {
   a.count = n;
   a.dcount = list_n;
   const dim3 g((unsigned)std::max(1, c->cu_count * 2));
-#define GP_FIN_TAIL(WW)                                                                                 \
-  if (weighted) hipLaunchKernelGGL((k_bitcount_tail<WW, true>), g, dim3(BC_BLOCK), 0, s, a, 0, cov, fwd); \
-  else hipLaunchKernelGGL((k_bitcount_tail<WW, false>), g, dim3(BC_BLOCK), 0, s, a, 0, cov, fwd);
-  switch (W) {
-    case 1: GP_FIN_TAIL(1) break;
-    case 2: GP_FIN_TAIL(2) break;
-    case 4: GP_FIN_TAIL(4) break;
-    case 8: GP_FIN_TAIL(8) break;
-    case 16: GP_FIN_TAIL(16) break;
-    case 32: GP_FIN_TAIL(32) break;
-    case 64: GP_FIN_TAIL(64) break;
-    default: return set_error(GP_EINVAL, "unsupported word count");
-  }
-#undef GP_FIN_TAIL
+  GP_TRY(with_words(W, [&](auto w) {
+    if (weighted) hipLaunchKernelGGL((k_bitcount_tail<w(), true>), g, dim3(BC_BLOCK), 0, s, a, 0, cov, fwd);
+    else hipLaunchKernelGGL((k_bitcount_tail<w(), false>), g, dim3(BC_BLOCK), 0, s, a, 0, cov, fwd);
+  }));
   GP_HIP(hipGetLastError());
   return 0;
 }

@@ -241,17 +241,9 @@ int gp_checkpoint_load(gp_ctx* c, const void* host, int64_t bytes) {
   c->prev_receivers = h.prev_receivers;
   c->held_bits = h.held_bits;
   c->last_reports = h.last_reports;
-  // the spread curve is not in the blob (as the job record): a
-  // run restored at round 0 has counted nothing yet and keeps the cleared one
-  if (h.round > 0) c->curve_valid = false;
-  load_restored(c, h.round);   // (nor the per-peer loads of an eager run, load.hip)
-  fresh_restored(c, h.round);  // (nor the fresh deliveries, fresh.hip)
-  fresh_curve_restored(c, h.round);   // (nor their per-message curve, fresh_curve.hip)
-  link_restored(c, h.round);   // (nor the per-link record, link.hip)
-  delay_restored(c, h.round);  // (nor the receipt delays, delay.hip)
-  delay_dist_restored(c, h.round);   // (nor their distributions, delay_dist.hip)
-  mult_restored(c, h.round);   // (nor the delivery multiplicity, mult.hip)
-  watch_restored(c, h.round);  // (nor the watched peers' arrivals, watch.hip)
+  // no per-run record is in the blob (as the job record): a run
+  // restored at round 0 has counted nothing yet and keeps the cleared ones
+  records_restored(c, h.round);
   return 0;
 }
 

@@ -125,7 +125,7 @@ __global__ void k_curve_inject(const int32_t* __restrict__ origin, const u64* __
 }
 
 int curve_alloc(Ctx* c, bool on) {
-  c->curve_valid = false;
+  c->rec[R_CURVE].valid = false;   // (a new buffer holds no run's counts)
   c->curve_alloc = false;
   if (!on) {
     dfree(&c->d_curve);
@@ -137,12 +137,17 @@ int curve_alloc(Ctx* c, bool on) {
   return 0;
 }
 
-int curve_reset(Ctx* c) {
-  c->curve_on = c->curve_alloc && c->d_curve != nullptr;
-  c->curve_valid = c->curve_on;
-  if (c->curve_on)
-    GP_HIP(hipMemsetAsync(c->d_curve, 0, (size_t)CURVE_ROWS * c->words * 64 * 8, c->stream));
+// gp_reset: cleared, counted from here on.  The buffer is alloc_state's
+// (curve_alloc), which gp_reset has run whenever the request changed
+static int curve_reset(Ctx* c) {
+  if (!c->curve_alloc || !c->d_curve) return set_error(GP_ESTATE, "internal: spread curve without its buffer");
+  GP_HIP(hipMemsetAsync(c->d_curve, 0, (size_t)CURVE_ROWS * c->words * 64 * 8, c->stream));
   return 0;
+}
+
+static void curve_free(Ctx* c) {
+  (void)curve_alloc(c, false);
+  record_off(c->rec[R_CURVE]);
 }
 
 int curve_env_grid() {
@@ -165,16 +170,7 @@ static int launch_curve(Ctx* c, u64* out) {
   const int64_t count = c->nloc();
   const u64* rows = c->d_frx[c->cur ^ 1];
   const uint32_t* guard = c->d_fpop[c->cur ^ 1];
-  switch (c->words) {
-    case 1: launch_curve_w<1>(c, rows, guard, count, out); break;
-    case 2: launch_curve_w<2>(c, rows, guard, count, out); break;
-    case 4: launch_curve_w<4>(c, rows, guard, count, out); break;
-    case 8: launch_curve_w<8>(c, rows, guard, count, out); break;
-    case 16: launch_curve_w<16>(c, rows, guard, count, out); break;
-    case 32: launch_curve_w<32>(c, rows, guard, count, out); break;
-    case 64: launch_curve_w<64>(c, rows, guard, count, out); break;
-    default: return set_error(GP_EINVAL, "unsupported word count");
-  }
+  GP_TRY(with_words(c->words, [&](auto w) { launch_curve_w<w()>(c, rows, guard, count, out); }));
   GP_HIP(hipGetLastError());
   return 0;
 }
@@ -222,11 +218,10 @@ static int curve_yardstick(Ctx* c, u64* out) {
 }
 
 // after E_r (and before the exchange moves on): rows r and r + 1 of the curve
-int curve_count_round(Ctx* c) {
-  if (!c->curve_on || !c->curve_valid) return 0;
+static int curve_count_round(Ctx* c) {
   const int r = c->round;
-  if (r + 1 >= CURVE_ROWS || !c->d_frx[0] || c->frx_rows < c->nloc())
-    return set_error(GP_ESTATE, "internal: spread curve without frontier rows");
+  if (r + 1 >= CURVE_ROWS) return set_error(GP_ESTATE, "internal: spread curve past its last row");
+  GP_TRY(record_need_rows(c, curve_record, c->nloc()));
   const size_t M = (size_t)c->words * 64;
   hipStream_t s = c->stream;
   auto it = c->inject.find(r);
@@ -240,17 +235,17 @@ int curve_count_round(Ctx* c) {
   return c->curve_yard ? curve_yardstick(c, out) : launch_curve(c, out);
 }
 
+// (kept by a partitioned context for its owned slice)
+GP_RECORD_OPS(curve_record) = {R_CURVE, "spread curve", "gp_track_curve", false, 0, nullptr, nullptr, curve_reset,
+                                curve_free, curve_count_round, nullptr, nullptr};
+
 }  // namespace gp
 
 using namespace gp;
 
 extern "C" {
 
-int gp_track_curve(gp_ctx* c, int32_t on) {
-  if (!c) return set_error(GP_EINVAL, "null ctx");
-  c->curve_want = on != 0;   // (allocated, and counted from, the next gp_reset)
-  return 0;
-}
+int gp_track_curve(gp_ctx* c, int32_t on) { return record_track(c, curve_record, on); }
 
 int gp_read_curve(gp_ctx* c, int32_t job, uint64_t* host, int32_t cap_rows, int32_t* rows_out) {
   if (!c || !host || !rows_out) return set_error(GP_EINVAL, "null argument");
@@ -265,9 +260,7 @@ int gp_read_curve(gp_ctx* c, int32_t job, uint64_t* host, int32_t cap_rows, int3
     *rows_out = c->j_curve_rows;
     return 0;
   }
-  if (!c->curve_on || !state_ready(c)) return set_error(GP_ENOTRACK, "gp_track_curve, then gp_reset");
-  if (!c->curve_valid)
-    return set_error(GP_ESTATE, "the run was restored past round 0: its spread curve was not kept (gp_reset)");
+  GP_TRY(record_readable(c, curve_record));
   const int32_t rows = c->round + 1;
   if (cap_rows < rows) return set_error(GP_EINVAL, "cap_rows < " + std::to_string(rows) + " rows");
   GP_HIP(hipStreamSynchronize(c->stream));

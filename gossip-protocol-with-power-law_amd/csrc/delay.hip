@@ -219,13 +219,13 @@ bool delay_env_rows() {
   return e && e[0] == '1';
 }
 
-void delay_free(Ctx* c) {
+static void delay_free(Ctx* c) {
   dfree(&c->d_delay_sum);
   dfree(&c->d_delay_max);
   dfree(&c->d_delay_planes);
   dfree(&c->d_delay_bins);
   c->delay_rows = 0;
-  c->delay_on = c->delay_valid = false;
+  record_off(c->rec[R_DELAY]);
 }
 
 // gp_reset: gp_track_delay takes effect (u32 and u8 per owned vertex, the
@@ -233,11 +233,7 @@ void delay_free(Ctx* c) {
 // follow the owned slice, so another overlay or partition re-sizes them; the
 // planes are rebuilt from the context's own table, so a message shard gets its
 // own.  The frontier rows of the general path are alloc_state's (setup.hip)
-int delay_reset(Ctx* c) {
-  if (!c->delay_want) {
-    delay_free(c);
-    return 0;
-  }
+static int delay_reset(Ctx* c) {
   const size_t nl = (size_t)std::max<int64_t>(c->nloc(), 1);
   if (!c->d_delay_sum || c->delay_rows != nl) {
     delay_free(c);
@@ -250,8 +246,7 @@ int delay_reset(Ctx* c) {
   }
   if ((int32_t)c->h_inj_round.size() != c->m) return set_error(GP_ESTATE, "internal: receipt delays without a message table");
   if (c->delay_by_rows()) {
-    if (!c->d_frx[0] || c->frx_rows < c->nloc())
-      return set_error(GP_ESTATE, "internal: receipt delays without frontier rows");
+    GP_TRY(record_need_rows(c, delay_record, c->nloc()));
     std::vector<uint64_t> planes((size_t)DELAY_PLANES * c->words);
     delay_build_planes(c->h_inj_round.data(), c->m, c->words, planes.data());
     if (dalloc(&c->d_delay_planes, planes.size()) != 0) {
@@ -264,7 +259,6 @@ int delay_reset(Ctx* c) {
   }
   GP_HIP(hipMemsetAsync(c->d_delay_sum, 0, nl * 4, c->stream));
   GP_HIP(hipMemsetAsync(c->d_delay_max, 0, nl, c->stream));
-  c->delay_on = c->delay_valid = true;
   return 0;
 }
 
@@ -278,8 +272,8 @@ static void launch_delay_w(Ctx* c, int64_t count, uint32_t rr) {
 }
 
 // after E_r: the first receipts of round r, receipt round r + 1
-int delay_count_round(Ctx* c) {
-  if (!c->delay_on || !c->delay_valid || c->nloc() <= 0) return 0;
+static int delay_count_round(Ctx* c) {
+  if (c->nloc() <= 0) return 0;
   const int64_t count = c->nloc();
   const uint32_t rr = (uint32_t)c->round + 1u;
   if (!c->delay_by_rows()) {
@@ -290,37 +284,21 @@ int delay_count_round(Ctx* c) {
     GP_HIP(hipGetLastError());
     return 0;
   }
-  if (!c->d_frx[0] || c->frx_rows < count || !c->d_delay_planes)
-    return set_error(GP_ESTATE, "internal: receipt delays without frontier rows");
-  switch (c->words) {
-    case 1: launch_delay_w<1>(c, count, rr); break;
-    case 2: launch_delay_w<2>(c, count, rr); break;
-    case 4: launch_delay_w<4>(c, count, rr); break;
-    case 8: launch_delay_w<8>(c, count, rr); break;
-    case 16: launch_delay_w<16>(c, count, rr); break;
-    case 32: launch_delay_w<32>(c, count, rr); break;
-    case 64: launch_delay_w<64>(c, count, rr); break;
-    default: return set_error(GP_EINVAL, "unsupported word count");
-  }
+  GP_TRY(record_need_rows(c, delay_record, count));
+  if (!c->d_delay_planes) return set_error(GP_ESTATE, "internal: receipt delays without inject-round planes");
+  GP_TRY(with_words(c->words, [&](auto w) { launch_delay_w<w()>(c, count, rr); }));
   GP_HIP(hipGetLastError());
   return 0;
 }
 
-// gp_checkpoint_load restored the run at `round`: the record is not in the blob
-void delay_restored(Ctx* c, int32_t round) {
-  if (c->delay_on && round > 0) c->delay_valid = false;
-}
-
-// the reads' common refusals
-static int delay_readable(Ctx* c) {
-  if (!c->delay_on || !state_ready(c)) return set_error(GP_ENOTRACK, "gp_track_delay, then gp_reset");
-  if (!c->delay_valid)
-    return set_error(GP_ESTATE, "the run was restored past round 0: its receipt delays were not kept (gp_reset)");
-  return 0;
-}
+// (a partitioned context keeps it for its owned slice; the rows only for a
+// table of several inject rounds)
+static bool delay_frx(const Ctx* c) { return c->delay_needs_rows(); }
+GP_RECORD_OPS(delay_record) = {R_DELAY, "receipt delays", "gp_track_delay", false, 0, nullptr, delay_frx, delay_reset,
+                                delay_free, delay_count_round, nullptr, nullptr};
 
 int delay_read(Ctx* c, int32_t what, void* host, int64_t bytes) {
-  GP_TRY(delay_readable(c));
+  GP_TRY(record_readable(c, delay_record));
   const int64_t nl = c->nloc();
   const int64_t want = what == GP_DELAY_SUM ? nl * 4 : nl;
   if (bytes != want) return set_error(GP_EINVAL, "bytes mismatch: expected " + std::to_string(want));
@@ -335,15 +313,11 @@ using namespace gp;
 
 extern "C" {
 
-int gp_track_delay(gp_ctx* c, int32_t on) {
-  if (!c) return set_error(GP_EINVAL, "null ctx");
-  c->delay_want = on != 0;   // (allocated, and counted from, the next gp_reset)
-  return 0;
-}
+int gp_track_delay(gp_ctx* c, int32_t on) { return record_track(c, delay_record, on); }
 
 int gp_read_delay_bins(gp_ctx* c, uint64_t* out, int32_t bins) {
   if (!c || !out) return set_error(GP_EINVAL, "null argument");
-  GP_TRY(delay_readable(c));
+  GP_TRY(record_readable(c, delay_record));
   if (bins != DELAY_BIN_ROWS) return set_error(GP_EINVAL, "bins must be " + std::to_string(DELAY_BIN_ROWS));
   GP_HIP(hipSetDevice(c->device));
   constexpr size_t BYTES = (size_t)DELAY_BIN_ROWS * DELAY_BIN_COLS * 8;

@@ -221,23 +221,19 @@ __global__ __launch_bounds__(BLOCK) void k_delay_dist_bins(const int64_t* __rest
   }
 }
 
-void delay_dist_free(Ctx* c) {
+static void delay_dist_free(Ctx* c) {
   dfree(&c->d_ddist);
   dfree(&c->d_ddist_planes);
   dfree(&c->d_ddist_bins);
   c->ddist_rows = 0;
-  c->ddist_on = c->ddist_valid = false;
+  record_off(c->rec[R_DELAY_DIST]);
 }
 
 // gp_reset: gp_track_delay_dist takes effect (32 B per owned vertex, the
 // table's planes and presence set, the bins' device result -- or nothing),
 // cleared.  As delay_reset: the array follows the owned slice, the planes and
 // the presence set are the context's own table's, so a message shard gets its own
-int delay_dist_reset(Ctx* c) {
-  if (!c->ddist_want) {
-    delay_dist_free(c);
-    return 0;
-  }
+static int delay_dist_reset(Ctx* c) {
   const size_t nl = (size_t)std::max<int64_t>(c->nloc(), 1);
   if (!c->d_ddist || c->ddist_rows != nl) {
     delay_dist_free(c);
@@ -252,8 +248,7 @@ int delay_dist_reset(Ctx* c) {
   const DelayPresent present = delay_present_build(c->h_inj_round.data(), c->m);
   std::memcpy(c->ddist_present, present.w, sizeof(c->ddist_present));
   if (c->delay_by_rows()) {
-    if (!c->d_frx[0] || c->frx_rows < c->nloc())
-      return set_error(GP_ESTATE, "internal: delay distributions without frontier rows");
+    GP_TRY(record_need_rows(c, delay_dist_record, c->nloc()));
     std::vector<uint64_t> planes((size_t)DELAY_PLANES * c->words);
     delay_build_planes(c->h_inj_round.data(), c->m, c->words, planes.data());
     if (dalloc(&c->d_ddist_planes, planes.size()) != 0) {
@@ -265,7 +260,6 @@ int delay_dist_reset(Ctx* c) {
     dfree(&c->d_ddist_planes);
   }
   GP_HIP(hipMemsetAsync(c->d_ddist, 0, nl * DELAY_DIST_BINS * 2, c->stream));
-  c->ddist_on = c->ddist_valid = true;
   return 0;
 }
 
@@ -279,8 +273,8 @@ static void launch_delay_dist_w(Ctx* c, int64_t count, uint32_t rr, const DelayW
 }
 
 // after E_r: the first receipts of round r, receipt round r + 1
-int delay_dist_count_round(Ctx* c) {
-  if (!c->ddist_on || !c->ddist_valid || c->nloc() <= 0) return 0;
+static int delay_dist_count_round(Ctx* c) {
+  if (c->nloc() <= 0) return 0;
   const int64_t count = c->nloc();
   const uint32_t rr = (uint32_t)c->round + 1u;
   if (!c->delay_by_rows()) {
@@ -292,37 +286,21 @@ int delay_dist_count_round(Ctx* c) {
     GP_HIP(hipGetLastError());
     return 0;
   }
-  if (!c->d_frx[0] || c->frx_rows < count || !c->d_ddist_planes)
-    return set_error(GP_ESTATE, "internal: delay distributions without frontier rows");
+  GP_TRY(record_need_rows(c, delay_dist_record, count));
+  if (!c->d_ddist_planes) return set_error(GP_ESTATE, "internal: delay distributions without inject-round planes");
   DelayPresent present;
   std::memcpy(present.w, c->ddist_present, sizeof(present.w));
   const DelayWindow win = delay_window(present, rr);
-  switch (c->words) {
-    case 1: launch_delay_dist_w<1>(c, count, rr, win); break;
-    case 2: launch_delay_dist_w<2>(c, count, rr, win); break;
-    case 4: launch_delay_dist_w<4>(c, count, rr, win); break;
-    case 8: launch_delay_dist_w<8>(c, count, rr, win); break;
-    case 16: launch_delay_dist_w<16>(c, count, rr, win); break;
-    case 32: launch_delay_dist_w<32>(c, count, rr, win); break;
-    case 64: launch_delay_dist_w<64>(c, count, rr, win); break;
-    default: return set_error(GP_EINVAL, "unsupported word count");
-  }
+  GP_TRY(with_words(c->words, [&](auto w) { launch_delay_dist_w<w()>(c, count, rr, win); }));
   GP_HIP(hipGetLastError());
   return 0;
 }
 
-// gp_checkpoint_load restored the run at `round`: the record is not in the blob
-void delay_dist_restored(Ctx* c, int32_t round) {
-  if (c->ddist_on && round > 0) c->ddist_valid = false;
-}
-
-// the reads' common refusals
-static int delay_dist_readable(Ctx* c) {
-  if (!c->ddist_on || !state_ready(c)) return set_error(GP_ENOTRACK, "gp_track_delay_dist, then gp_reset");
-  if (!c->ddist_valid)
-    return set_error(GP_ESTATE, "the run was restored past round 0: its delay distributions were not kept (gp_reset)");
-  return 0;
-}
+// (as delay_record: kept by a partitioned context, rows for several inject rounds only)
+static bool delay_dist_frx(const Ctx* c) { return c->delay_needs_rows(); }
+GP_RECORD_OPS(delay_dist_record) = {R_DELAY_DIST, "delay distributions", "gp_track_delay_dist", false, 0, nullptr,
+                                     delay_dist_frx, delay_dist_reset, delay_dist_free, delay_dist_count_round, nullptr,
+                                     nullptr};
 
 // both reads start here: column 0 from the counters
 static int delay_dist_column0(Ctx* c) {
@@ -336,7 +314,7 @@ static int delay_dist_column0(Ctx* c) {
 }
 
 int delay_dist_read(Ctx* c, void* host, int64_t bytes) {
-  GP_TRY(delay_dist_readable(c));
+  GP_TRY(record_readable(c, delay_dist_record));
   const int64_t want = c->nloc() * DELAY_DIST_BINS * 2;
   if (bytes != want) return set_error(GP_EINVAL, "bytes mismatch: expected " + std::to_string(want));
   if (bytes == 0) return 0;
@@ -351,15 +329,11 @@ using namespace gp;
 
 extern "C" {
 
-int gp_track_delay_dist(gp_ctx* c, int32_t on) {
-  if (!c) return set_error(GP_EINVAL, "null ctx");
-  c->ddist_want = on != 0;   // (allocated, and counted from, the next gp_reset)
-  return 0;
-}
+int gp_track_delay_dist(gp_ctx* c, int32_t on) { return record_track(c, delay_dist_record, on); }
 
 int gp_read_delay_dist_bins(gp_ctx* c, uint64_t* out, int32_t bins) {
   if (!c || !out) return set_error(GP_EINVAL, "null argument");
-  GP_TRY(delay_dist_readable(c));
+  GP_TRY(record_readable(c, delay_dist_record));
   if (bins != DDIST_BIN_ROWS) return set_error(GP_EINVAL, "bins must be " + std::to_string(DDIST_BIN_ROWS));
   GP_HIP(hipSetDevice(c->device));
   constexpr size_t BYTES = (size_t)DDIST_BIN_ROWS * DDIST_BIN_COLS * 8;

@@ -300,11 +300,8 @@ V(1) V(2) V(4) V(8) V(16) V(32) V(64)
 // force (lag_prepare makes it so) -- or the reset is refused
 int lag_reset(Ctx* c) {
   if (c->lag_want) {
-    const char* rec = c->load_want ? "gp_track_load" : c->fresh_want ? "gp_track_fresh"
-                    : c->fresh_curve_want ? "gp_track_fresh_curve" : c->link_want ? "gp_track_link_fresh"
-                    : c->mult_want ? "gp_track_mult" : c->watch_want() ? "gp_watch" : nullptr;
-    if (rec)
-      return set_error(GP_EINVAL, std::string("link delay is on and so is ") + rec +
+    if (const RecordOps* rec = records_arc_walker(c))
+      return set_error(GP_EINVAL, std::string("link delay is on and so is ") + rec->call +
                                       ": the record walks arcs and takes every line to arrive in its send round");
     if (c->local || c->nranks > 1)
       return set_error(GP_EINVAL, "link delay is not supported in a vertex-partitioned context");

@@ -367,7 +367,7 @@ static void fill_expand(Ctx* c, ExpandArgs& a) {
   // (the push reads the senders' exact rows where some other output keeps them;
   // rows kept for gp_track_fresh, gp_track_fresh_curve or gp_track_link_fresh alone leave its source, and
   // so every work counter of the run, the untracked run's)
-  const bool frx_src = c->cfg.track_msg_forwards != 0 || c->local || c->curve_want;
+  const bool frx_src = c->cfg.track_msg_forwards != 0 || c->local || c->rec[R_CURVE].want;
   a.frx = c->d_frx[0] && frx_src ? c->d_frx[c->cur] : nullptr;
   a.frx_next = c->d_frx[0] ? c->d_frx[c->cur ^ 1] : nullptr;
   a.frx_rows = c->frx_rows;
@@ -520,16 +520,7 @@ static void launch_bitsum_w(Ctx* c, BitsumArgs a, bool cnt, bool sum) {
 
 static int launch_bitsum(Ctx* c, BitsumArgs a, bool cnt, bool sum) {
   if (a.count <= 0) return 0;
-  switch (c->words) {
-    case 1: launch_bitsum_w<1>(c, a, cnt, sum); break;
-    case 2: launch_bitsum_w<2>(c, a, cnt, sum); break;
-    case 4: launch_bitsum_w<4>(c, a, cnt, sum); break;
-    case 8: launch_bitsum_w<8>(c, a, cnt, sum); break;
-    case 16: launch_bitsum_w<16>(c, a, cnt, sum); break;
-    case 32: launch_bitsum_w<32>(c, a, cnt, sum); break;
-    case 64: launch_bitsum_w<64>(c, a, cnt, sum); break;
-    default: return set_error(GP_EINVAL, "unsupported word count");
-  }
+  GP_TRY(with_words(c->words, [&](auto w) { launch_bitsum_w<w()>(c, a, cnt, sum); }));
   GP_HIP(hipGetLastError());
   return 0;
 }
@@ -617,21 +608,14 @@ static int round_launch(Ctx* c) {
     b.count = c->nloc();
     GP_TRY(launch_bitsum(c, b, false, true));
   }
-  GP_TRY(load_count_round(c));   // (nothing is launched unless gp_track_load is on and the run counts per round)
+  GP_TRY(load_before_expand(c));   // (nothing is launched unless gp_track_load is on and the run counts per round)
 
   GP_HIP(hipEventRecord(c->ev[1], s));
   GP_TRY(launch_expand(c));
   hipLaunchKernelGGL(k_stats_reduce, dim3(NST), dim3(BLOCK), 0, s, partial, stats);
   GP_HIP(hipGetLastError());
   GP_HIP(hipEventRecord(c->ev[2], s));
-  GP_TRY(curve_count_round(c));   // (nothing is launched unless gp_track_curve is on)
-  GP_TRY(fresh_count_round(c));   // (... gp_track_fresh)
-  GP_TRY(mult_count_round(c));    // (... gp_track_mult)
-  GP_TRY(fresh_curve_count_round(c));   // (... gp_track_fresh_curve)
-  GP_TRY(link_count_round(c));   // (... gp_track_link_fresh)
-  GP_TRY(delay_count_round(c));   // (... gp_track_delay)
-  GP_TRY(delay_dist_count_round(c));   // (... gp_track_delay_dist)
-  return watch_count_round(c);   // (... gp_watch; all after expand_ms ends: round_ms carries them)
+  return records_count_round(c);   // (nothing is launched unless a record is on; all after expand_ms ends: round_ms carries them)
 }
 
 // X_r over RCCL.  One rank: the counters' all-reduce is the whole exchange.

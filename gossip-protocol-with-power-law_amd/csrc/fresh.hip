@@ -162,21 +162,15 @@ bool fresh_env_gather() {
   return e && e[0] == '1';
 }
 
-static bool fresh_wanted(const Ctx* c) { return c->fresh_want && c->nranks == 1; }
-
-void fresh_free(Ctx* c) {
+static void fresh_free(Ctx* c) {
   dfree(&c->d_fresh_sent);
   dfree(&c->d_fresh_recv);
-  c->fresh_on = c->fresh_valid = false;
+  record_off(c->rec[R_FRESH]);
 }
 
 // gp_reset: gp_track_fresh takes effect (two u64[n], or none), cleared.  The
 // exact frontier rows are alloc_state's (setup.hip: frx_rows)
-int fresh_reset(Ctx* c) {
-  if (!fresh_wanted(c)) {
-    fresh_free(c);
-    return 0;
-  }
+static int fresh_reset(Ctx* c) {
   if (!c->d_fresh_sent) {
     const size_t n = (size_t)c->n;
     if (dalloc(&c->d_fresh_sent, n) != 0 || dalloc(&c->d_fresh_recv, n) != 0) {
@@ -186,7 +180,6 @@ int fresh_reset(Ctx* c) {
   }
   GP_HIP(hipMemsetAsync(c->d_fresh_sent, 0, (size_t)c->n * 8, c->stream));
   GP_HIP(hipMemsetAsync(c->d_fresh_recv, 0, (size_t)c->n * 8, c->stream));
-  c->fresh_on = c->fresh_valid = true;
   return 0;
 }
 
@@ -200,25 +193,15 @@ static void launch_fresh_w(Ctx* c, const FreshArgs& a) {
 
 template <bool SCATTER>
 static int launch_fresh(Ctx* c, const FreshArgs& a) {
-  switch (c->words) {
-    case 1: launch_fresh_w<1, SCATTER>(c, a); break;
-    case 2: launch_fresh_w<2, SCATTER>(c, a); break;
-    case 4: launch_fresh_w<4, SCATTER>(c, a); break;
-    case 8: launch_fresh_w<8, SCATTER>(c, a); break;
-    case 16: launch_fresh_w<16, SCATTER>(c, a); break;
-    case 32: launch_fresh_w<32, SCATTER>(c, a); break;
-    case 64: launch_fresh_w<64, SCATTER>(c, a); break;
-    default: return set_error(GP_EINVAL, "unsupported word count");
-  }
+  GP_TRY(with_words(c->words, [&](auto w) { launch_fresh_w<w(), SCATTER>(c, a); }));
   GP_HIP(hipGetLastError());
   return 0;
 }
 
 // after E_r: round r's deliveries that were first receipts, per receiver and per sender
-int fresh_count_round(Ctx* c) {
-  if (!c->fresh_on || !c->fresh_valid || c->n <= 0) return 0;
-  if (!c->d_frx[0] || c->frx_rows < c->n)
-    return set_error(GP_ESTATE, "internal: fresh deliveries without frontier rows");
+static int fresh_count_round(Ctx* c) {
+  if (c->n <= 0) return 0;
+  GP_TRY(record_need_rows(c, fresh_record, c->n));
   const int cur = c->cur;
   FreshArgs a{};
   a.items = c->d_hub_items;
@@ -245,18 +228,11 @@ int fresh_count_round(Ctx* c) {
   return launch_fresh<false>(c, a);
 }
 
-// gp_checkpoint_load restored the run at `round`: the totals are not in the
-// blob and are no function of the restored state
-void fresh_restored(Ctx* c, int32_t round) {
-  if (c->fresh_on && round > 0) c->fresh_valid = false;
-}
+GP_RECORD_OPS(fresh_record) = {R_FRESH, "fresh deliveries", "gp_track_fresh", true, 2, nullptr, nullptr, fresh_reset,
+                                fresh_free, fresh_count_round, nullptr, nullptr};
 
 int fresh_read(Ctx* c, int32_t what, void* host, int64_t bytes) {
-  if (c->nranks > 1)
-    return set_error(GP_ENOTRACK, "fresh deliveries are not kept by a vertex-partitioned context");
-  if (!c->fresh_on || !state_ready(c)) return set_error(GP_ENOTRACK, "gp_track_fresh, then gp_reset");
-  if (!c->fresh_valid)
-    return set_error(GP_ESTATE, "the run was restored past round 0: its fresh deliveries were not kept (gp_reset)");
+  GP_TRY(record_readable(c, fresh_record));
   if (bytes != c->n * 8) return set_error(GP_EINVAL, "bytes mismatch: expected " + std::to_string(c->n * 8));
   return copy_sync(c, host, what == GP_FRESH_SENT ? c->d_fresh_sent : c->d_fresh_recv, (size_t)bytes,
                    hipMemcpyDeviceToHost);
@@ -268,10 +244,6 @@ using namespace gp;
 
 extern "C" {
 
-int gp_track_fresh(gp_ctx* c, int32_t on) {
-  if (!c) return set_error(GP_EINVAL, "null ctx");
-  c->fresh_want = on != 0;   // (allocated, and counted from, the next gp_reset)
-  return 0;
-}
+int gp_track_fresh(gp_ctx* c, int32_t on) { return record_track(c, fresh_record, on); }
 
 }  // extern "C"

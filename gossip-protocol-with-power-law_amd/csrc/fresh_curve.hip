@@ -253,21 +253,15 @@ int fresh_curve_env_grid() {
   return k >= 1 && k <= (1 << 20) ? (int)k : 0;
 }
 
-static bool fresh_curve_wanted(const Ctx* c) { return c->fresh_curve_want && c->nranks == 1; }
-
-void fresh_curve_free(Ctx* c) {
+static void fresh_curve_free(Ctx* c) {
   dfree(&c->d_fresh_curve);
   c->fresh_curve_words = 0;
-  c->fresh_curve_on = c->fresh_curve_valid = false;
+  record_off(c->rec[R_FRESH_CURVE]);
 }
 
 // gp_reset: gp_track_fresh_curve takes effect ([255][W * 64] u64, or nothing),
 // cleared.  The exact frontier rows are alloc_state's (setup.hip: frx_rows)
-int fresh_curve_reset(Ctx* c) {
-  if (!fresh_curve_wanted(c)) {
-    fresh_curve_free(c);
-    return 0;
-  }
+static int fresh_curve_reset(Ctx* c) {
   if (c->nnz >= (int64_t)1 << 32) {   // (the u32 LDS counts of a block: header)
     fresh_curve_free(c);
     return set_error(GP_EINVAL, "gp_track_fresh_curve: an overlay of 2^32 arcs or more is not counted");
@@ -279,7 +273,6 @@ int fresh_curve_reset(Ctx* c) {
     c->fresh_curve_words = words;
   }
   GP_HIP(hipMemsetAsync(c->d_fresh_curve, 0, words * 8, c->stream));
-  c->fresh_curve_on = c->fresh_curve_valid = true;
   return 0;
 }
 
@@ -295,11 +288,11 @@ static void launch_fresh_curve_w(Ctx* c, const FreshCurveArgs& a) {
 }
 
 // after E_r: row r + 1, the deliverers of round r's first receipts per message
-int fresh_curve_count_round(Ctx* c) {
-  if (!c->fresh_curve_on || !c->fresh_curve_valid || c->n <= 0) return 0;
+static int fresh_curve_count_round(Ctx* c) {
+  if (c->n <= 0) return 0;
   const int r = c->round;
-  if (r + 1 >= FRESH_CURVE_ROWS || !c->d_frx[0] || c->frx_rows < c->n)
-    return set_error(GP_ESTATE, "internal: fresh-delivery curve without frontier rows");
+  if (r + 1 >= FRESH_CURVE_ROWS) return set_error(GP_ESTATE, "internal: fresh-delivery curve past its last row");
+  GP_TRY(record_need_rows(c, fresh_curve_record, c->n));
   const int cur = c->cur;
   FreshCurveArgs a{};
   a.row_ptr = c->d_row_ptr;
@@ -313,25 +306,14 @@ int fresh_curve_count_round(Ctx* c) {
   a.n = c->n;
   a.n_items = c->n_hub_items;
   a.hub_thr = c->cfg.hub_threshold;
-  switch (c->words) {
-    case 1: launch_fresh_curve_w<1>(c, a); break;
-    case 2: launch_fresh_curve_w<2>(c, a); break;
-    case 4: launch_fresh_curve_w<4>(c, a); break;
-    case 8: launch_fresh_curve_w<8>(c, a); break;
-    case 16: launch_fresh_curve_w<16>(c, a); break;
-    case 32: launch_fresh_curve_w<32>(c, a); break;
-    case 64: launch_fresh_curve_w<64>(c, a); break;
-    default: return set_error(GP_EINVAL, "unsupported word count");
-  }
+  GP_TRY(with_words(c->words, [&](auto w) { launch_fresh_curve_w<w()>(c, a); }));
   GP_HIP(hipGetLastError());
   return 0;
 }
 
-// gp_checkpoint_load restored the run at `round`: the record is not in the
-// blob and is no function of the restored state
-void fresh_curve_restored(Ctx* c, int32_t round) {
-  if (c->fresh_curve_on && round > 0) c->fresh_curve_valid = false;
-}
+GP_RECORD_OPS(fresh_curve_record) = {R_FRESH_CURVE, "fresh-delivery curves", "gp_track_fresh_curve", true, 3, nullptr,
+                                      nullptr, fresh_curve_reset, fresh_curve_free, fresh_curve_count_round, nullptr,
+                                      nullptr};
 
 }  // namespace gp
 
@@ -339,20 +321,11 @@ using namespace gp;
 
 extern "C" {
 
-int gp_track_fresh_curve(gp_ctx* c, int32_t on) {
-  if (!c) return set_error(GP_EINVAL, "null ctx");
-  c->fresh_curve_want = on != 0;   // (allocated, and counted from, the next gp_reset)
-  return 0;
-}
+int gp_track_fresh_curve(gp_ctx* c, int32_t on) { return record_track(c, fresh_curve_record, on); }
 
 int gp_read_fresh_curve(gp_ctx* c, uint64_t* host, int32_t cap_rows, int32_t* rows_out) {
   if (!c || !host || !rows_out) return set_error(GP_EINVAL, "null argument");
-  if (c->nranks > 1)
-    return set_error(GP_ENOTRACK, "fresh-delivery curves are not kept by a vertex-partitioned context");
-  if (!c->fresh_curve_on || !state_ready(c)) return set_error(GP_ENOTRACK, "gp_track_fresh_curve, then gp_reset");
-  if (!c->fresh_curve_valid)
-    return set_error(GP_ESTATE,
-                     "the run was restored past round 0: its fresh-delivery curve was not kept (gp_reset)");
+  GP_TRY(record_readable(c, fresh_curve_record));
   const int32_t rows = c->round + 1;
   if (cap_rows < rows) return set_error(GP_EINVAL, "cap_rows < " + std::to_string(rows) + " rows");
   GP_HIP(hipSetDevice(c->device));

@@ -7,10 +7,12 @@
 #include <cstdint>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gossip_capi.h"
 #include "gp_common.h"
+#include "records.h"
 #include "round_plan.h"
 
 namespace gp {
@@ -137,64 +139,50 @@ struct Ctx {
   // (carry.park_failed: it could not be)
   uint8_t* d_sp = nullptr;          // [n_alloc] slot of v's seen row (0xFF: none)
   uint8_t* d_ws = nullptr;          // [n_alloc] bit p: slot p written this run
-  u64* d_frx[2] = {nullptr, nullptr};     // exact frontier rows (track_msg_forwards; partitioned; spread curve; fresh deliveries; lossy links)
+  u64* d_frx[2] = {nullptr, nullptr};     // exact frontier rows, kept while anyone wants them (records.h frx_users)
   int64_t frx_rows = 0;                   // rows d_frx covers (partitioned: the owned ones)
+  uint32_t frx_sized = 0;                 // frx_users() when alloc_state sized them
+  // the per-run records' request / in force / valid flags (records.h), by RecordId
+  RecordState rec[R_COUNT];
   // spread curve (curve.hip): [255][W * 64] first receipts per
-  // receipt round and message over the owned vertices.  curve_want is what
-  // gp_track_curve asked for, curve_alloc what alloc_state made, curve_on what
-  // the run since the last gp_reset counts; curve_valid falls when a
-  // checkpoint restores the run past round 0 (the curve is not in the blob)
+  // receipt round and message over the owned vertices.  alloc_state makes the
+  // buffer with the run state (it follows the row width): curve_alloc
   u64* d_curve = nullptr;
-  bool curve_want = false, curve_alloc = false, curve_on = false, curve_valid = false;
+  bool curve_alloc = false;
   int curve_grid = 0;                     // GP_CURVE_GRID at gp_create: cap of k_curve's grid (0: none)
   bool curve_yard = false;                // GP_CURVE_YARDSTICK=1 at gp_create: time k_curve beside k_bitsum
   // per-peer traffic record (load.hip): lines sent / received
   // per vertex since gp_reset, and the lazy read's scratch (x = seenpop - fpop).
-  // load_want is what gp_track_load asked for, load_on what the run since the
-  // last gp_reset keeps (single-rank contexts only); load_valid falls when a
-  // checkpoint restores an eager run past round 0 (the totals are not in the blob)
+  // A lazy run's totals are a function of its state: a restore keeps them
   u64* d_load_sent = nullptr;             // [n]
   u64* d_load_recv = nullptr;             // [n]
   uint32_t* d_load_x = nullptr;           // [n]
-  bool load_want = false, load_on = false, load_valid = false;
   bool load_force = false;                // GP_LOAD_EAGER=1 at gp_create: count per round from round 0
   // per-peer fresh deliveries (fresh.hip): of those lines, the
   // ones that carried a first receipt, per sender and per receiver since
-  // gp_reset.  fresh_want is what gp_track_fresh asked for, fresh_alloc what
-  // alloc_state sized the frontier rows for, fresh_on what the run since the
-  // last gp_reset keeps (single-rank contexts only); fresh_valid falls when a
-  // checkpoint restores the run past round 0 (the totals are not in the blob)
+  // gp_reset
   u64* d_fresh_sent = nullptr;            // [n]
   u64* d_fresh_recv = nullptr;            // [n]
-  bool fresh_want = false, fresh_alloc = false, fresh_on = false, fresh_valid = false;
   bool fresh_gather = false;              // GP_FRESH_GATHER=1 at gp_create: undirected overlays gather once per role
   // fresh-delivery curve (fresh_curve.hip): [255][W * 64] the
   // deliverers of every message's first receipts per receipt round, the
-  // per-message split of fresh_recv.  The four flags are the fresh
-  // deliveries': what gp_track_fresh_curve asked for, what alloc_state sized
-  // the frontier rows for, what the run since the last gp_reset keeps
-  // (single-rank contexts only), and whether a restore past round 0 lost it
+  // per-message split of fresh_recv
   u64* d_fresh_curve = nullptr;
   size_t fresh_curve_words = 0;           // u64 d_fresh_curve holds
-  bool fresh_curve_want = false, fresh_curve_alloc = false, fresh_curve_on = false, fresh_curve_valid = false;
   int fresh_curve_grid = 0;               // GP_FRESH_CURVE_GRID at gp_create: cap of k_fresh_curve's grid (0: none)
   // per-link fresh deliveries (link.hip): the same news per arc
   // of the in-CSR, the matrix d_fresh_sent / d_fresh_recv are the column / row
   // sums of.  u16 per arc: over a run arc u -> v counts a message at most once
   // (v receives it for the first time once), so link_fresh[j] <= m <= 4096 --
-  // and a path with every message injected at one end attains it.  The four
-  // flags are the fresh deliveries'
+  // and a path with every message injected at one end attains it
   uint16_t* d_link = nullptr;             // [nnz] in-CSR arc order
   u64* d_link_hist = nullptr;             // [4097] gp_read_link_hist's device result
   size_t link_arcs = 0;                   // arcs d_link holds
-  bool link_want = false, link_alloc = false, link_on = false, link_valid = false;
   // per-peer receipt delays (delay.hip): over the owned
   // vertices, the sum and the maximum of first[v][k] - inject_round[k] over the
-  // messages v holds.  delay_want is what gp_track_delay asked for, delay_alloc
-  // whether alloc_state sized the frontier rows for it (a table whose messages
-  // all start in one round needs none: delay_uniform), delay_on what the run
-  // since the last gp_reset keeps, delay_valid falls when a checkpoint restores
-  // the run past round 0.  Partitioned contexts keep it for their owned slice
+  // messages v holds.  A table whose messages all start in one round needs no
+  // frontier rows (delay_uniform).  Partitioned contexts keep it for their
+  // owned slice
   uint32_t* d_delay_sum = nullptr;        // [nloc]
   uint8_t* d_delay_max = nullptr;         // [nloc]
   u64* d_delay_planes = nullptr;          // [8][W] inject-round planes of the context's table (delay_planes.h)
@@ -202,25 +190,23 @@ struct Ctx {
   size_t delay_rows = 0;                  // vertices the two arrays hold
   std::vector<uint8_t> h_inj_round;       // [m] inject round of every message of the context's table
   int32_t delay_uniform = -1;             // the table's one inject round (-1: they differ)
-  bool delay_want = false, delay_alloc = false, delay_on = false, delay_valid = false;
   bool delay_force_rows = false;          // GP_DELAY_ROWS=1 at gp_create: the row pass for a one-round table too
   bool delay_by_rows() const { return delay_uniform < 0 || delay_force_rows; }
   // per-peer delay distributions (delay_dist.hip): the same
   // receipts per delay value, u16 [nloc][16] (delays 0 .. 14, 15 or more).  The
-  // flags are the receipt delays'; the two records are independent, share
-  // delay_uniform / delay_force_rows, and either one with a table of several
-  // inject rounds makes alloc_state keep the frontier rows (delay_alloc)
+  // two records are independent, share delay_uniform / delay_force_rows, and
+  // either one with a table of several inject rounds keeps the frontier rows
   uint16_t* d_ddist = nullptr;            // [nloc][16]
   u64* d_ddist_planes = nullptr;          // [8][W] inject-round planes of the context's table
   u64* d_ddist_bins = nullptr;            // [32][16] gp_read_delay_dist_bins' device result
   uint64_t ddist_present[4] = {0, 0, 0, 0};   // the table's inject rounds as a 256-bit set (delay_dist.h)
   size_t ddist_rows = 0;                  // vertices the array holds
-  bool ddist_want = false, ddist_on = false, ddist_valid = false;
-  bool delay_needs_rows() const { return (delay_want || ddist_want) && delay_by_rows(); }
+  bool delay_needs_rows() const {
+    return delay_rows_needed(rec[R_DELAY].want, rec[R_DELAY_DIST].want, delay_uniform, delay_force_rows);
+  }
   // delivery multiplicity (mult.hip): how many in-neighbours
   // delivered each first receipt -- the histogram of that number, and per peer
-  // the receipts with one deliverer, as receiver and as that deliverer.  The
-  // four flags are the fresh deliveries' (single-rank contexts only)
+  // the receipts with one deliverer, as receiver and as that deliverer
   uint32_t* d_sole_recv = nullptr;        // [n]
   u64* d_sole_sent = nullptr;             // [n]
   u64* d_mult_hist = nullptr;             // [256][17] copies of the histogram (bin 0 unused: the injections)
@@ -228,14 +214,10 @@ struct Ctx {
   u64* d_mult_scratch = nullptr;          // [n_hub_items][5][W] the hub items' counters of one round
   u64* d_mult_hub_sole = nullptr;         // [n_hubs][W] the hubs' sole masks of one round
   size_t mult_rows = 0, mult_scratch_words = 0, mult_hub_words = 0;   // what the arrays were sized for
-  bool mult_want = false, mult_alloc = false, mult_on = false, mult_valid = false;
   // watched peers (watch.hip): the arrival log of a caller-chosen
   // list of peers, one byte per (in-arc, message) and per (peer, message).
   // h_watch_want is what gp_watch set, for the next gp_reset; h_watch_v /
-  // h_watch_ptr are the list in force and its arc offsets.  watch_alloc is
-  // whether alloc_state sized the frontier rows for it, watch_on what the run
-  // since the last gp_reset keeps (single-rank contexts only), watch_valid falls
-  // when a checkpoint restores the run past round 0
+  // h_watch_ptr are the list in force and its arc offsets
   std::vector<int32_t> h_watch_want, h_watch_v;
   std::vector<int64_t> h_watch_ptr;       // [K + 1]
   int64_t watch_max_bytes = 0;            // gp_watch's budget for the two byte arrays
@@ -247,28 +229,25 @@ struct Ctx {
   uint8_t* d_watch_arrival = nullptr;     // [A][W * 64]
   int64_t watch_arcs = 0;                 // A
   int32_t watch_words = 0;                // the row width the arrays were made for
-  bool watch_alloc = false, watch_on = false, watch_valid = false;
   bool watch_want() const { return !h_watch_want.empty(); }
   // lossy links (lossy.hip): every arc drops the lines of
   // a round with probability p, by a draw of the ordered pair and the round.
   // loss_want / loss_p_want / loss_seed_want are what gp_link_loss asked for,
-  // loss_alloc whether alloc_state sized the frontier rows for it, loss_on /
-  // loss_p / loss_seed the setting of the run since the last gp_reset
+  // loss_on / loss_p / loss_seed the setting of the run since the last gp_reset
   // (single-rank contexts only)
-  bool loss_want = false, loss_alloc = false, loss_on = false;
+  bool loss_want = false, loss_on = false;
   double loss_p_want = 0.0, loss_p = 0.0;
   uint64_t loss_seed_want = 0, loss_seed = 0;
   // delayed links (delayed.hip): the link between u and
   // v takes d(u, v) in [1, dmax] rounds, fixed for the run (link_delay.h).
   // lag_want / lag_dmax_want / lag_seed_want are what gp_link_delay asked for,
-  // lag_alloc whether alloc_state sized the frontier rows for it, lag_on /
-  // lag_dmax / lag_seed the setting of the run since the last gp_reset
+  // lag_on / lag_dmax / lag_seed the setting of the run since the last gp_reset
   // (single-rank contexts only).  While the ring is in force (lag_ring > 0) it
   // owns every frontier-row buffer: d_lag_frx[0] and [1] are alloc_state's two,
   // the rest its own, and d_frx[cur] / d_frx[cur ^ 1] are rotated through them
   // each round (lag_rotate); lag_release hands the first two back to d_frx
   // before anything frees or reallocates them
-  bool lag_want = false, lag_alloc = false, lag_on = false;
+  bool lag_want = false, lag_on = false;
   int32_t lag_dmax_want = 1, lag_dmax = 1;
   uint64_t lag_seed_want = 0, lag_seed = 0;
   uint32_t lag_hist = 0;               // bit k: round - 1 - k of this run had a sender (lag_in_flight)
@@ -277,10 +256,7 @@ struct Ctx {
   u64* d_lag_bits = nullptr;              // [lag_dmax + 1][lag_nw] k_mkbits' bitmap of round s in row s % lag_dmax; last row: their OR
   int64_t lag_nw = 0;                     // words per bitmap row
   uint8_t* d_lag_arc = nullptr;           // [nnz] d(u, v) per arc of the in-CSR
-  bool holds_frx() const {
-    return cfg.track_msg_forwards != 0 || local || curve_want || fresh_want || fresh_curve_want || link_want ||
-           delay_needs_rows() || mult_want || watch_want() || loss_want || lag_want;
-  }
+  bool holds_frx() const { return frx_users(this) != 0; }
   uint32_t* d_fpop[2] = {nullptr, nullptr};    // [n_alloc]
   int cur = 0;
   uint32_t* d_seenpop = nullptr;    // [nloc]
@@ -464,6 +440,22 @@ int set_error(int code, const std::string& msg);
 #define GP_TRY(expr)                                                              \
   do { int _rc = (expr); if (_rc != 0) return _rc; } while (0)
 
+// f(std::integral_constant<int, W>{}) for the row width `words`, one of the
+// seven the kernels are built for; any other is GP_EINVAL
+template <class F>
+int with_words(int words, F&& f) {
+  switch (words) {
+    case 1: f(std::integral_constant<int, 1>{}); return 0;
+    case 2: f(std::integral_constant<int, 2>{}); return 0;
+    case 4: f(std::integral_constant<int, 4>{}); return 0;
+    case 8: f(std::integral_constant<int, 8>{}); return 0;
+    case 16: f(std::integral_constant<int, 16>{}); return 0;
+    case 32: f(std::integral_constant<int, 32>{}); return 0;
+    case 64: f(std::integral_constant<int, 64>{}); return 0;
+    default: return set_error(GP_EINVAL, "unsupported word count");
+  }
+}
+
 template <class T>
 int dalloc(T** p, size_t count) {
   if (*p) { (void)hipFree(*p); *p = nullptr; }
@@ -499,63 +491,23 @@ int finalize_by_components(Ctx* c, bool weighted, u64* cov, u64* fwd);   // the 
 void bitcount_free(Ctx* c);
 // curve.hip
 int curve_alloc(Ctx* c, bool on);              // with the run state: the count buffer (or none)
-int curve_reset(Ctx* c);                       // new run: cleared, counted from here on
-int curve_count_round(Ctx* c);                 // after E_r: rows r (injections) and r + 1 (first receipts)
 int curve_env_grid();                          // GP_CURVE_GRID in the environment (0: unset)
 bool curve_env_yardstick();                    // GP_CURVE_YARDSTICK=1 in the environment
-// load.hip
-int load_reset(Ctx* c);                        // gp_reset: gp_track_load takes effect; buffers (or none), cleared
-void load_free(Ctx* c);
-int load_count_round(Ctx* c);                  // after L_r and I_r of an eager run: round r's sends and arrivals
+// load.hip: the traffic record's hooks outside the table's walks (records.h)
+int load_before_expand(Ctx* c);                // after L_r and I_r of an eager run: round r's sends and arrivals
 int load_before_liveness(Ctx* c);              // gp_crash turns liveness on: a lazy run books its rounds so far
-void load_restored(Ctx* c, int32_t round);     // gp_checkpoint_load: an eager run past round 0 lost its totals
-int load_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_LOAD_SENT / GP_LOAD_RECV
 bool load_env_eager();                         // GP_LOAD_EAGER=1 in the environment
-// fresh.hip
-int fresh_reset(Ctx* c);                       // gp_reset: gp_track_fresh takes effect; buffers (or none), cleared
-void fresh_free(Ctx* c);
-int fresh_count_round(Ctx* c);                 // after E_r: round r's first-receipt deliveries per sender / receiver
-void fresh_restored(Ctx* c, int32_t round);    // gp_checkpoint_load: a run past round 0 lost its totals
+// the records' typed reads behind gp_read (each in its record's unit)
+int load_read(Ctx* c, int32_t what, void* host, int64_t bytes);    // GP_LOAD_SENT / GP_LOAD_RECV
 int fresh_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_FRESH_SENT / GP_FRESH_RECV
-bool fresh_env_gather();                       // GP_FRESH_GATHER=1 in the environment
-// fresh_curve.hip
-int fresh_curve_reset(Ctx* c);                 // gp_reset: gp_track_fresh_curve takes effect; the record (or none), cleared
-void fresh_curve_free(Ctx* c);
-int fresh_curve_count_round(Ctx* c);           // after E_r: row r + 1, the deliverers of round r's first receipts
-void fresh_curve_restored(Ctx* c, int32_t round);   // gp_checkpoint_load: a run past round 0 lost its record
-int fresh_curve_env_grid();                    // GP_FRESH_CURVE_GRID in the environment (0: unset)
-// link.hip
-int link_reset(Ctx* c);                        // gp_reset: gp_track_link_fresh takes effect; the record (or none), cleared
-void link_free(Ctx* c);
-int link_count_round(Ctx* c);                  // after E_r: round r's first-receipt deliveries per arc of the in-CSR
-void link_restored(Ctx* c, int32_t round);     // gp_checkpoint_load: a run past round 0 lost its record
-int link_read(Ctx* c, void* host, int64_t bytes);   // GP_LINK_FRESH
-// delay.hip
-int delay_reset(Ctx* c);                       // gp_reset: gp_track_delay takes effect; the record (or none), cleared
-void delay_free(Ctx* c);
-int delay_count_round(Ctx* c);                 // after E_r: the delays of round r's first receipts, per receiver
-void delay_restored(Ctx* c, int32_t round);    // gp_checkpoint_load: a run past round 0 lost its record
-bool delay_env_rows();                         // GP_DELAY_ROWS=1 in the environment
+int link_read(Ctx* c, void* host, int64_t bytes);                  // GP_LINK_FRESH
 int delay_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_DELAY_SUM / GP_DELAY_MAX
-// delay_dist.hip
-int delay_dist_reset(Ctx* c);                  // gp_reset: gp_track_delay_dist takes effect; the record (or none), cleared
-void delay_dist_free(Ctx* c);
-int delay_dist_count_round(Ctx* c);            // after E_r: round r's first receipts per receiver and delay value
-void delay_dist_restored(Ctx* c, int32_t round);   // gp_checkpoint_load: a run past round 0 lost its record
-int delay_dist_read(Ctx* c, void* host, int64_t bytes);   // GP_DELAY_DIST
-// mult.hip
-int mult_reset(Ctx* c);                        // gp_reset: gp_track_mult takes effect; the record (or none), cleared
-void mult_free(Ctx* c);
-int mult_count_round(Ctx* c);                  // after E_r: the deliverer counts of round r's first receipts
-void mult_restored(Ctx* c, int32_t round);     // gp_checkpoint_load: a run past round 0 lost its record
-int mult_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_SOLE_SENT / GP_SOLE_RECV
-// watch.hip
-int watch_reset(Ctx* c);                       // gp_reset: gp_watch's list takes effect; the record (or none), filled with 255
-void watch_free(Ctx* c);
-void watch_forget(Ctx* c);                     // a new overlay: the list's ids were the old one's
-int watch_count_round(Ctx* c);                 // after E_r: round r's arrivals at the watched peers, link by link
-void watch_restored(Ctx* c, int32_t round);    // gp_checkpoint_load: a run past round 0 lost its record
+int delay_dist_read(Ctx* c, void* host, int64_t bytes);            // GP_DELAY_DIST
+int mult_read(Ctx* c, int32_t what, void* host, int64_t bytes);    // GP_SOLE_SENT / GP_SOLE_RECV
 int watch_read(Ctx* c, int32_t what, void* host, int64_t bytes);   // GP_WATCH_FIRST / GP_WATCH_ARRIVAL / GP_WATCH_PTR
+bool fresh_env_gather();                       // GP_FRESH_GATHER=1 in the environment
+int fresh_curve_env_grid();                    // GP_FRESH_CURVE_GRID in the environment (0: unset)
+bool delay_env_rows();                         // GP_DELAY_ROWS=1 in the environment
 // lossy.hip
 int loss_reset(Ctx* c);                        // gp_reset: gp_link_loss takes effect, or the reset is refused
 // delayed.hip

@@ -199,24 +199,18 @@ static int64_t link_hist_grid(const Ctx* c, int64_t nnz) {
   return grid;
 }
 
-static bool link_wanted(const Ctx* c) { return c->link_want && c->nranks == 1; }
-
-void link_free(Ctx* c) {
+static void link_free(Ctx* c) {
   dfree(&c->d_link);
   dfree(&c->d_link_hist);
   c->link_arcs = 0;
-  c->link_on = c->link_valid = false;
+  record_off(c->rec[R_LINK]);
 }
 
 // gp_reset: gp_track_link_fresh takes effect (u16[nnz] and the histogram's
 // u64[4097], or nothing), cleared.  A new overlay freed the array
 // (finish_graph), so it is sized for the arcs of this one.  The exact frontier
 // rows are alloc_state's (setup.hip: frx_rows)
-int link_reset(Ctx* c) {
-  if (!link_wanted(c)) {
-    link_free(c);
-    return 0;
-  }
+static int link_reset(Ctx* c) {
   const size_t arcs = (size_t)c->nnz;
   if (!c->d_link || c->link_arcs != arcs) {
     link_free(c);
@@ -227,7 +221,6 @@ int link_reset(Ctx* c) {
     c->link_arcs = arcs;
   }
   if (arcs) GP_HIP(hipMemsetAsync(c->d_link, 0, arcs * sizeof(uint16_t), c->stream));
-  c->link_on = c->link_valid = true;
   return 0;
 }
 
@@ -239,10 +232,9 @@ static void launch_link_w(Ctx* c, const LinkArgs& a) {
 }
 
 // after E_r: round r's first-receipt deliveries, added to the arcs they came over
-int link_count_round(Ctx* c) {
-  if (!c->link_on || !c->link_valid || c->n <= 0 || c->nnz <= 0) return 0;
-  if (!c->d_frx[0] || c->frx_rows < c->n)
-    return set_error(GP_ESTATE, "internal: per-link fresh deliveries without frontier rows");
+static int link_count_round(Ctx* c) {
+  if (c->n <= 0 || c->nnz <= 0) return 0;
+  GP_TRY(record_need_rows(c, link_record, c->n));
   const int cur = c->cur;
   LinkArgs a{};
   a.row_ptr = c->d_row_ptr;
@@ -256,39 +248,16 @@ int link_count_round(Ctx* c) {
   a.n = c->n;
   a.n_items = c->n_hub_items;
   a.hub_thr = c->cfg.hub_threshold;
-  switch (c->words) {
-    case 1: launch_link_w<1>(c, a); break;
-    case 2: launch_link_w<2>(c, a); break;
-    case 4: launch_link_w<4>(c, a); break;
-    case 8: launch_link_w<8>(c, a); break;
-    case 16: launch_link_w<16>(c, a); break;
-    case 32: launch_link_w<32>(c, a); break;
-    case 64: launch_link_w<64>(c, a); break;
-    default: return set_error(GP_EINVAL, "unsupported word count");
-  }
+  GP_TRY(with_words(c->words, [&](auto w) { launch_link_w<w()>(c, a); }));
   GP_HIP(hipGetLastError());
   return 0;
 }
 
-// gp_checkpoint_load restored the run at `round`: the record is not in the
-// blob and is no function of the restored state
-void link_restored(Ctx* c, int32_t round) {
-  if (c->link_on && round > 0) c->link_valid = false;
-}
-
-// the reads' common refusals (fresh_read's)
-static int link_readable(Ctx* c) {
-  if (c->nranks > 1)
-    return set_error(GP_ENOTRACK, "per-link fresh deliveries are not kept by a vertex-partitioned context");
-  if (!c->link_on || !state_ready(c)) return set_error(GP_ENOTRACK, "gp_track_link_fresh, then gp_reset");
-  if (!c->link_valid)
-    return set_error(GP_ESTATE,
-                     "the run was restored past round 0: its per-link fresh deliveries were not kept (gp_reset)");
-  return 0;
-}
+GP_RECORD_OPS(link_record) = {R_LINK, "per-link fresh deliveries", "gp_track_link_fresh", true, 4, nullptr, nullptr,
+                               link_reset, link_free, link_count_round, nullptr, nullptr};
 
 int link_read(Ctx* c, void* host, int64_t bytes) {
-  GP_TRY(link_readable(c));
+  GP_TRY(record_readable(c, link_record));
   if (bytes != c->nnz * 2) return set_error(GP_EINVAL, "bytes mismatch: expected " + std::to_string(c->nnz * 2));
   if (bytes == 0) return 0;
   return copy_sync(c, host, c->d_link, (size_t)bytes, hipMemcpyDeviceToHost);
@@ -300,15 +269,11 @@ using namespace gp;
 
 extern "C" {
 
-int gp_track_link_fresh(gp_ctx* c, int32_t on) {
-  if (!c) return set_error(GP_EINVAL, "null ctx");
-  c->link_want = on != 0;   // (allocated, and counted from, the next gp_reset)
-  return 0;
-}
+int gp_track_link_fresh(gp_ctx* c, int32_t on) { return record_track(c, link_record, on); }
 
 int gp_read_link_hist(gp_ctx* c, uint64_t* hist, int32_t bins) {
   if (!c || !hist) return set_error(GP_EINVAL, "null argument");
-  GP_TRY(link_readable(c));
+  GP_TRY(record_readable(c, link_record));
   if (bins != LINK_BINS) return set_error(GP_EINVAL, "bins must be " + std::to_string(LINK_BINS));
   GP_HIP(hipSetDevice(c->device));
   GP_HIP(hipMemsetAsync(c->d_link_hist, 0, (size_t)LINK_BINS * 8, c->stream));

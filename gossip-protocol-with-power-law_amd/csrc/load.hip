@@ -183,21 +183,15 @@ bool load_env_eager() {
   return e && e[0] == '1';
 }
 
-static bool load_wanted(const Ctx* c) { return c->load_want && c->nranks == 1; }
-
-void load_free(Ctx* c) {
+static void load_free(Ctx* c) {
   dfree(&c->d_load_sent);
   dfree(&c->d_load_recv);
   dfree(&c->d_load_x);
-  c->load_on = c->load_valid = false;
+  record_off(c->rec[R_LOAD]);
 }
 
 // gp_reset: gp_track_load takes effect (two u64[n] and one u32[n], or none), cleared
-int load_reset(Ctx* c) {
-  if (!load_wanted(c)) {
-    load_free(c);
-    return 0;
-  }
+static int load_reset(Ctx* c) {
   if (!c->d_load_sent) {
     const size_t n = (size_t)c->n;
     if (dalloc(&c->d_load_sent, n) != 0 || dalloc(&c->d_load_recv, n) != 0 || dalloc(&c->d_load_x, n) != 0) {
@@ -207,7 +201,6 @@ int load_reset(Ctx* c) {
   }
   GP_HIP(hipMemsetAsync(c->d_load_sent, 0, (size_t)c->n * 8, c->stream));
   GP_HIP(hipMemsetAsync(c->d_load_recv, 0, (size_t)c->n * 8, c->stream));
-  c->load_on = c->load_valid = true;
   return 0;
 }
 
@@ -245,10 +238,12 @@ static int launch_load(Ctx* c, const uint32_t* x, int probe) {
 
 // the run counts per round: some vertex may be down, or the lever says so
 static bool load_eager(const Ctx* c) { return c->load_force || c->liveness_active; }
+static bool load_lazy(const Ctx* c) { return !load_eager(c); }
+static bool load_counting(const Ctx* c) { return c->rec[R_LOAD].on && c->rec[R_LOAD].valid; }
 
 // round r, after L_r and I_r: fpop[cur] is |frontier_r|, state and deg_live are E_r's
-int load_count_round(Ctx* c) {
-  if (!c->load_on || !c->load_valid || !load_eager(c)) return 0;
+int load_before_expand(Ctx* c) {
+  if (!load_counting(c) || !load_eager(c)) return 0;
   // this round's senders are last round's receivers and this round's origins
   // (crashes aside), and the arcs that leave them are the gathers a probe
   // cannot save.  The choice moves time only: every variant adds the same.
@@ -278,22 +273,20 @@ static int load_flush(Ctx* c) {
 // gp_crash is about to turn liveness on in a lazy run: the rounds so far are
 // booked once, before the crash is applied; the run is eager from here on
 int load_before_liveness(Ctx* c) {
-  if (!c->load_on || !c->load_valid || load_eager(c)) return 0;
+  if (!load_counting(c) || load_eager(c)) return 0;
   return load_flush(c);
 }
 
-// gp_checkpoint_load restored the run at `round`: the accumulators are not in
-// the blob.  A lazy run needs none; an eager one past round 0 has lost its own
-void load_restored(Ctx* c, int32_t round) {
-  if (c->load_on && round > 0 && load_eager(c)) c->load_valid = false;
-}
+// No count_round: the eager pass runs before the expansion (load_before_expand).
+// The accumulators are not in a checkpoint's blob: a lazy run needs none (its
+// totals are a function of the restored state), an eager one past round 0 has
+// lost its own.  The pass reads no frontier rows
+static bool load_no_rows(const Ctx*) { return false; }
+GP_RECORD_OPS(load_record) = {R_LOAD, "per-peer loads", "gp_track_load", true, 1, nullptr, load_no_rows, load_reset,
+                               load_free, nullptr, nullptr, load_lazy};
 
 int load_read(Ctx* c, int32_t what, void* host, int64_t bytes) {
-  if (c->nranks > 1)
-    return set_error(GP_ENOTRACK, "per-peer loads are not kept by a vertex-partitioned context");
-  if (!c->load_on || !state_ready(c)) return set_error(GP_ENOTRACK, "gp_track_load, then gp_reset");
-  if (!c->load_valid)
-    return set_error(GP_ESTATE, "the run was restored past round 0: its per-round loads were not kept (gp_reset)");
+  GP_TRY(record_readable(c, load_record));
   if (bytes != c->n * 8) return set_error(GP_EINVAL, "bytes mismatch: expected " + std::to_string(c->n * 8));
   if (!load_eager(c)) GP_TRY(load_flush(c));
   return copy_sync(c, host, what == GP_LOAD_SENT ? c->d_load_sent : c->d_load_recv, (size_t)bytes,
@@ -306,10 +299,6 @@ using namespace gp;
 
 extern "C" {
 
-int gp_track_load(gp_ctx* c, int32_t on) {
-  if (!c) return set_error(GP_EINVAL, "null ctx");
-  c->load_want = on != 0;   // (allocated, and counted from, the next gp_reset)
-  return 0;
-}
+int gp_track_load(gp_ctx* c, int32_t on) { return record_track(c, load_record, on); }
 
 }  // extern "C"

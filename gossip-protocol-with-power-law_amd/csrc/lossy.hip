@@ -317,11 +317,8 @@ V(1) V(2) V(4) V(8) V(16) V(32) V(64)
 // gp_reset: the request becomes the setting in force -- or the reset is refused
 int loss_reset(Ctx* c) {
   if (c->loss_want) {
-    const char* rec = c->load_want ? "gp_track_load" : c->fresh_want ? "gp_track_fresh"
-                    : c->fresh_curve_want ? "gp_track_fresh_curve" : c->link_want ? "gp_track_link_fresh"
-                    : c->mult_want ? "gp_track_mult" : c->watch_want() ? "gp_watch" : nullptr;
-    if (rec)
-      return set_error(GP_EINVAL, std::string("link loss is on and so is ") + rec +
+    if (const RecordOps* rec = records_arc_walker(c))
+      return set_error(GP_EINVAL, std::string("link loss is on and so is ") + rec->call +
                                       ": the record walks arcs and would count closed ones as deliveries");
     if (c->local || c->nranks > 1)
       return set_error(GP_EINVAL, "link loss is not supported in a vertex-partitioned context");

@@ -382,9 +382,7 @@ __global__ __launch_bounds__(BLOCK) void k_sole_bins(const int64_t* __restrict__
     if (tb[t]) atomicAdd(&out[t], tb[t]);
 }
 
-static bool mult_wanted(const Ctx* c) { return c->mult_want && c->nranks == 1; }
-
-void mult_free(Ctx* c) {
+static void mult_free(Ctx* c) {
   dfree(&c->d_sole_recv);
   dfree(&c->d_sole_sent);
   dfree(&c->d_mult_hist);
@@ -392,7 +390,7 @@ void mult_free(Ctx* c) {
   dfree(&c->d_mult_scratch);
   dfree(&c->d_mult_hub_sole);
   c->mult_rows = c->mult_scratch_words = c->mult_hub_words = 0;
-  c->mult_on = c->mult_valid = false;
+  record_off(c->rec[R_MULT]);
 }
 
 // gp_reset: gp_track_mult takes effect (u32 + u64 per vertex, the histogram's
@@ -400,11 +398,7 @@ void mult_free(Ctx* c) {
 // The scratch follows the hub table and the row width, so another overlay,
 // hub_threshold or message table re-sizes it.  The exact frontier rows are
 // alloc_state's (setup.hip: frx_rows)
-int mult_reset(Ctx* c) {
-  if (!mult_wanted(c)) {
-    mult_free(c);
-    return 0;
-  }
+static int mult_reset(Ctx* c) {
   const size_t n = (size_t)c->n, W = (size_t)c->words;
   const size_t sw = (size_t)c->n_hub_items * MULT_WORDS * W, hw = (size_t)c->n_hubs * W;
   if (!c->d_sole_recv || c->mult_rows != n || c->mult_scratch_words != sw || c->mult_hub_words != hw) {
@@ -423,7 +417,6 @@ int mult_reset(Ctx* c) {
   GP_HIP(hipMemsetAsync(c->d_sole_recv, 0, std::max<size_t>(n, 1) * 4, c->stream));
   GP_HIP(hipMemsetAsync(c->d_sole_sent, 0, std::max<size_t>(n, 1) * 8, c->stream));
   GP_HIP(hipMemsetAsync(c->d_mult_hist, 0, (size_t)MULT_SLOTS * MULT_BINS * 8, c->stream));
-  c->mult_on = c->mult_valid = true;
   return 0;
 }
 
@@ -439,10 +432,9 @@ static void launch_mult_w(Ctx* c, const MultArgs& a) {
 }
 
 // after E_r: the deliverer counts of round r's first receipts
-int mult_count_round(Ctx* c) {
-  if (!c->mult_on || !c->mult_valid || c->n <= 0) return 0;
-  if (!c->d_frx[0] || c->frx_rows < c->n)
-    return set_error(GP_ESTATE, "internal: delivery multiplicity without frontier rows");
+static int mult_count_round(Ctx* c) {
+  if (c->n <= 0) return 0;
+  GP_TRY(record_need_rows(c, mult_record, c->n));
   if (c->mult_scratch_words != (size_t)c->n_hub_items * MULT_WORDS * (size_t)c->words ||
       c->mult_hub_words != (size_t)c->n_hubs * (size_t)c->words)
     return set_error(GP_ESTATE, "internal: delivery multiplicity scratch does not match the hub table");
@@ -466,37 +458,16 @@ int mult_count_round(Ctx* c) {
   a.n_items = c->n_hub_items;
   a.n_hubs = c->n_hubs;
   a.hub_thr = c->cfg.hub_threshold;
-  switch (c->words) {
-    case 1: launch_mult_w<1>(c, a); break;
-    case 2: launch_mult_w<2>(c, a); break;
-    case 4: launch_mult_w<4>(c, a); break;
-    case 8: launch_mult_w<8>(c, a); break;
-    case 16: launch_mult_w<16>(c, a); break;
-    case 32: launch_mult_w<32>(c, a); break;
-    case 64: launch_mult_w<64>(c, a); break;
-    default: return set_error(GP_EINVAL, "unsupported word count");
-  }
+  GP_TRY(with_words(c->words, [&](auto w) { launch_mult_w<w()>(c, a); }));
   GP_HIP(hipGetLastError());
   return 0;
 }
 
-// gp_checkpoint_load restored the run at `round`: the record is not in the blob
-void mult_restored(Ctx* c, int32_t round) {
-  if (c->mult_on && round > 0) c->mult_valid = false;
-}
-
-// the reads' common refusals
-static int mult_readable(Ctx* c) {
-  if (c->nranks > 1)
-    return set_error(GP_ENOTRACK, "the delivery multiplicity is not kept by a vertex-partitioned context");
-  if (!c->mult_on || !state_ready(c)) return set_error(GP_ENOTRACK, "gp_track_mult, then gp_reset");
-  if (!c->mult_valid)
-    return set_error(GP_ESTATE, "the run was restored past round 0: its delivery multiplicity was not kept (gp_reset)");
-  return 0;
-}
+GP_RECORD_OPS(mult_record) = {R_MULT, "delivery multiplicity", "gp_track_mult", true, 5, nullptr, nullptr, mult_reset,
+                               mult_free, mult_count_round, nullptr, nullptr};
 
 int mult_read(Ctx* c, int32_t what, void* host, int64_t bytes) {
-  GP_TRY(mult_readable(c));
+  GP_TRY(record_readable(c, mult_record));
   const int64_t want = what == GP_SOLE_SENT ? c->n * 8 : c->n * 4;
   if (bytes != want) return set_error(GP_EINVAL, "bytes mismatch: expected " + std::to_string(want));
   if (bytes == 0) return 0;
@@ -510,15 +481,11 @@ using namespace gp;
 
 extern "C" {
 
-int gp_track_mult(gp_ctx* c, int32_t on) {
-  if (!c) return set_error(GP_EINVAL, "null ctx");
-  c->mult_want = on != 0;   // (allocated, and counted from, the next gp_reset)
-  return 0;
-}
+int gp_track_mult(gp_ctx* c, int32_t on) { return record_track(c, mult_record, on); }
 
 int gp_read_mult_hist(gp_ctx* c, uint64_t* hist, int32_t bins) {
   if (!c || !hist) return set_error(GP_EINVAL, "null argument");
-  GP_TRY(mult_readable(c));
+  GP_TRY(record_readable(c, mult_record));
   if (bins != MULT_BINS) return set_error(GP_EINVAL, "bins must be " + std::to_string(MULT_BINS));
   GP_HIP(hipSetDevice(c->device));
   std::vector<u64> copies((size_t)MULT_SLOTS * MULT_BINS);
@@ -534,7 +501,7 @@ int gp_read_mult_hist(gp_ctx* c, uint64_t* hist, int32_t bins) {
 
 int gp_read_sole_bins(gp_ctx* c, uint64_t* out, int32_t bins) {
   if (!c || !out) return set_error(GP_EINVAL, "null argument");
-  GP_TRY(mult_readable(c));
+  GP_TRY(record_readable(c, mult_record));
   if (bins != SOLE_BIN_ROWS) return set_error(GP_EINVAL, "bins must be " + std::to_string(SOLE_BIN_ROWS));
   GP_HIP(hipSetDevice(c->device));
   constexpr size_t BYTES = (size_t)SOLE_BIN_ROWS * SOLE_BIN_COLS * 8;

@@ -536,16 +536,7 @@ static int launch_expand_w(Ctx* c, ExpandArgs a) {
 
 int launch_round_kernels(Ctx* c, const ExpandArgs& a) {
   int rc = PULL_OK;
-  switch (c->words) {
-    case 1: rc = launch_expand_w<1>(c, a); break;
-    case 2: rc = launch_expand_w<2>(c, a); break;
-    case 4: rc = launch_expand_w<4>(c, a); break;
-    case 8: rc = launch_expand_w<8>(c, a); break;
-    case 16: rc = launch_expand_w<16>(c, a); break;
-    case 32: rc = launch_expand_w<32>(c, a); break;
-    case 64: rc = launch_expand_w<64>(c, a); break;
-    default: return set_error(GP_EINVAL, "unsupported word count");
-  }
+  GP_TRY(with_words(c->words, [&](auto w) { rc = launch_expand_w<w()>(c, a); }));
   GP_HIP(hipGetLastError());
   if (rc == PULL_ORDER_FAILED) return set_error(GP_EHIP, "the hub chunks could not be ordered against the round's pull kernel");
   if (rc == PULL_NOT_BUILT) return set_error(GP_EINVAL, "the round chose a pull kernel that is not built for this row width");

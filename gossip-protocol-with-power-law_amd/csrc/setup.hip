@@ -248,16 +248,7 @@ static void free_state(Ctx* c) {
   dfree(&c->d_sp); dfree(&c->d_ws); dfree(&c->d_ldone);
   dfree(&c->d_ulist[0]); dfree(&c->d_ulist[1]);
   dfree(&c->d_seenpop); dfree(&c->d_first); dfree(&c->d_digest);
-  (void)curve_alloc(c, false);
-  c->curve_on = false;
-  load_free(c);
-  fresh_free(c);
-  fresh_curve_free(c);
-  link_free(c);
-  delay_free(c);
-  delay_dist_free(c);
-  mult_free(c);
-  watch_free(c);
+  records_free(c);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_abits); dfree(&c->d_dbits); dfree(&c->d_lm); dfree(&c->d_lmw[0]); dfree(&c->d_lmw[1]); dfree(&c->d_sbits); dfree(&c->d_amask); dfree(&c->d_cml[0]); dfree(&c->d_cml[1]); dfree(&c->d_cmk[0]); dfree(&c->d_cmk[1]); dfree(&c->d_done_at);
@@ -311,7 +302,7 @@ static int components(Ctx* c) {
 
 int finish_graph(Ctx* c) {
   free_state(c);
-  watch_forget(c);   // (gp_watch's ids were checked against the overlay this one replaces)
+  records_forget(c);   // (gp_watch's ids were checked against the overlay this one replaces)
   free_partition(c);   // a new overlay: partition again from the global CSR
   c->nnz_l = c->nnz;
   GP_TRY(dalloc(&c->d_deg_out, (size_t)c->n));
@@ -343,27 +334,13 @@ static int alloc_state(Ctx* c) {
   if (c->n <= 0) return set_error(GP_ESTATE, "no graph loaded");
   if (c->words <= 0) return set_error(GP_ESTATE, "no messages set");
   const size_t W = (size_t)c->words, na = (size_t)c->n_alloc, nl = (size_t)std::max<int64_t>(c->nloc(), 1);
-  // exact frontier rows only for per-message forwards (the pull reads whole
-  // Message-Lists) and for the boundary exchange of a vertex
-  // partition, which sends owned vertices' new bits: the owned rows only (a
-  // ghost's slot row is its frontier); the spread curve counts them too, and
-  // the fresh-delivery passes (fresh.hip, fresh_curve.hip, link.hip) intersect them
-  // (the receipt delays and their distributions read the receivers' own new rows, delay.hip, delay_dist.hip -- unless every message starts in one round)
-  const bool frx_record = c->cfg.track_msg_forwards || c->curve_want || c->fresh_want || c->fresh_curve_want ||
-                          c->link_want || c->delay_needs_rows() || c->mult_want ||   // (and mult.hip)
-                          c->watch_want() ||                                          // (and the watched peers, watch.hip)
-                          c->loss_want ||                                             // (lossy links read them, lossy.hip)
-                          c->lag_want;                                                // (and delayed links, delayed.hip)
+  // exact frontier rows only while someone reads them (records.h frx_users:
+  // the pull reads whole Message-Lists).  The boundary exchange
+  // of a vertex partition sends owned vertices' new bits: the owned rows only
+  // (a ghost's slot row is its frontier); every other user reads every vertex's
   lag_release(c);   // (before d_frx is reallocated: a ring may have rotated its pointers)
-  c->frx_rows = c->local ? c->nloc() : (frx_record ? c->n_alloc : 0);
-  c->fresh_alloc = c->fresh_want;
-  c->fresh_curve_alloc = c->fresh_curve_want;
-  c->link_alloc = c->link_want;
-  c->delay_alloc = c->delay_needs_rows();
-  c->mult_alloc = c->mult_want;
-  c->watch_alloc = c->watch_want();
-  c->loss_alloc = c->loss_want;
-  c->lag_alloc = c->lag_want;
+  c->frx_sized = frx_users(c);
+  c->frx_rows = c->local ? c->nloc() : (c->frx_sized ? c->n_alloc : 0);
   dfree(&c->d_slot[2]);   // (re)allocated at the first parking, for this W
   c->carry = RoundCarry{};   // (new buffers carry nothing over; parking may be tried again)
   // S[0] | S[1] | accumulator rows of the owned receivers, one allocation
@@ -437,7 +414,7 @@ static int alloc_state(Ctx* c) {
   GP_TRY(dalloc(&c->d_reports, (size_t)c->report_cap));
   GP_TRY(dalloc(&c->d_hub_partial, std::max<size_t>(c->h_hub_items.size(), 1) * W));
   if (c->local) GP_TRY(alloc_exchange(c));
-  GP_TRY(curve_alloc(c, c->curve_want));
+  GP_TRY(curve_alloc(c, c->rec[R_CURVE].want));
   GP_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -625,15 +602,8 @@ void gp_destroy(gp_ctx* c) {
   for (int k = 0; k < 2; ++k) { dfree(&c->d_frx[k]); dfree(&c->d_fpop[k]); }
   dfree(&c->d_sp); dfree(&c->d_ws); dfree(&c->d_ldone); dfree(&c->d_ld_cand);
   dfree(&c->d_ulist[0]); dfree(&c->d_ulist[1]);
-  dfree(&c->d_seenpop); dfree(&c->d_first); dfree(&c->d_digest); dfree(&c->d_curve);
-  load_free(c);
-  fresh_free(c);
-  fresh_curve_free(c);
-  link_free(c);
-  delay_free(c);
-  delay_dist_free(c);
-  mult_free(c);
-  watch_free(c);
+  dfree(&c->d_seenpop); dfree(&c->d_first); dfree(&c->d_digest);
+  records_free(c);
   dfree(&c->d_state); dfree(&c->d_miss); dfree(&c->d_deg_live); dfree(&c->d_cand);
   dfree(&c->d_det_big); dfree(&c->d_det_pre); dfree(&c->d_det_live); dfree(&c->d_det_cur); dfree(&c->d_det_base);
   dfree(&c->d_msg_cov); dfree(&c->d_reports); dfree(&c->d_stats);
@@ -907,15 +877,9 @@ int gp_reset(gp_ctx* c) {
   GP_HIP(hipSetDevice(c->device));
   GP_TRY(lag_reset(c));    // (gp_link_delay may refuse the reset, before anything changes; lag_prepare below applies it)
   GP_TRY(loss_reset(c));   // (gp_link_loss takes effect here -- or refuses the reset, before anything changes)
-  // (gp_track_curve, gp_track_fresh, gp_track_fresh_curve and gp_track_link_fresh take effect here: frontier
-  // rows, the count buffer)
-  if (!state_ready(c) || c->curve_alloc != c->curve_want || c->fresh_alloc != c->fresh_want ||
-      c->fresh_curve_alloc != c->fresh_curve_want || c->link_alloc != c->link_want ||
-      c->delay_alloc != c->delay_needs_rows() ||   // (gp_track_delay, gp_track_delay_dist: rows only for a table of several inject rounds)
-      c->mult_alloc != c->mult_want ||             // (gp_track_mult)
-      c->watch_alloc != c->watch_want() ||         // (gp_watch)
-      c->loss_alloc != c->loss_want ||             // (gp_link_loss)
-      c->lag_alloc != c->lag_want)                 // (gp_link_delay)
+  // (the records' requests, gp_link_loss and gp_link_delay take effect here: the frontier rows for who reads
+  // them now, the spread curve's buffer)
+  if (!state_ready(c) || c->frx_sized != frx_users(c) || c->curve_alloc != c->rec[R_CURVE].want)
     GP_TRY(alloc_state(c));
   if (!c->done_at_valid) {
     GP_TRY(compute_done_at(c, c->n_groups));
@@ -961,15 +925,7 @@ int gp_reset(gp_ctx* c) {
   c->msg_forwards_valid = true;
   c->last_reports = 0;
   shard_reset(c);
-  GP_TRY(curve_reset(c));
-  GP_TRY(load_reset(c));   // (gp_track_load takes effect here)
-  GP_TRY(fresh_reset(c));  // (and gp_track_fresh)
-  GP_TRY(fresh_curve_reset(c));   // (and gp_track_fresh_curve)
-  GP_TRY(link_reset(c));          // (and gp_track_link_fresh)
-  GP_TRY(delay_reset(c));         // (and gp_track_delay)
-  GP_TRY(delay_dist_reset(c));    // (and gp_track_delay_dist)
-  GP_TRY(mult_reset(c));          // (and gp_track_mult)
-  GP_TRY(watch_reset(c));         // (and gp_watch)
+  GP_TRY(records_reset(c));       // (every gp_track_* and gp_watch takes effect here)
   GP_TRY(lag_prepare(c));         // (and gp_link_delay: the ring of frontier rows, the arc delays)
   GP_HIP(hipStreamSynchronize(s));
   return 0;

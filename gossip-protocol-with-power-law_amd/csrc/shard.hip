@@ -325,7 +325,7 @@ int combine(Ctx* c, gp_round_stats* job, int32_t cap, int32_t* rounds_out, doubl
   hdr[H_DIRECTED] = (u64)c->directed;
   hdr[H_OK] = why.empty() ? 1 : 0;
   hdr[H_CAP] = (u64)cap;
-  hdr[H_CURVE] = c->curve_on && c->curve_valid ? 1 : 0;
+  hdr[H_CURVE] = c->rec[R_CURVE].on && c->rec[R_CURVE].valid ? 1 : 0;
   c->j_curve_valid = false;
   GP_TRY(copy_sync(c, c->d_jscr, hdr.data(), NH * 8, hipMemcpyHostToDevice));
   GP_TRY(x.allgather(c->d_jscr, c->d_jscr + NH, NH));

@@ -194,9 +194,7 @@ __global__ __launch_bounds__(64) void k_watch_build(const int64_t* __restrict__ 
   }
 }
 
-static bool watch_wanted(const Ctx* c) { return c->watch_want() && c->nranks == 1; }
-
-void watch_free(Ctx* c) {
+static void watch_free(Ctx* c) {
   dfree(&c->d_watch_v);
   dfree(&c->d_watch_ptr);
   dfree(&c->d_watch_col);
@@ -207,11 +205,11 @@ void watch_free(Ctx* c) {
   c->h_watch_ptr.clear();
   c->watch_arcs = 0;
   c->watch_words = 0;
-  c->watch_on = c->watch_valid = false;
+  record_off(c->rec[R_WATCH]);
 }
 
 // a new overlay: the ids of the list are another overlay's
-void watch_forget(Ctx* c) {
+static void watch_forget(Ctx* c) {
   watch_free(c);
   c->h_watch_want.clear();
 }
@@ -229,13 +227,9 @@ static int64_t watch_count_arcs(const Ctx* c, const std::vector<int32_t>& verts)
 // (re)built for the list, the overlay and the row width of this run, the record
 // filled with 0xFF; with no list nothing is allocated.  The exact frontier rows
 // are alloc_state's (setup.hip: frx_rows)
-int watch_reset(Ctx* c) {
-  if (!watch_wanted(c)) {
-    watch_free(c);
-    return 0;
-  }
+static int watch_reset(Ctx* c) {
   if (c->h_row_ptr.size() != (size_t)c->n + 1) return set_error(GP_ESTATE, "internal: watched peers without the overlay's offsets");
-  if (!c->d_frx[0] || c->frx_rows < c->n) return set_error(GP_ESTATE, "internal: watched peers without frontier rows");
+  GP_TRY(record_need_rows(c, watch_record, c->n));
   const std::vector<int32_t>& want = c->h_watch_want;
   const int64_t K = (int64_t)want.size(), A = watch_count_arcs(c, want);
   const int64_t need = watch_bytes(K, A, c->words);
@@ -270,7 +264,6 @@ int watch_reset(Ctx* c) {
   }
   GP_HIP(hipMemsetAsync(c->d_watch_first, 0xFF, (size_t)K * row, c->stream));
   if (A) GP_HIP(hipMemsetAsync(c->d_watch_arrival, 0xFF, (size_t)A * row, c->stream));
-  c->watch_on = c->watch_valid = true;
   return 0;
 }
 
@@ -282,10 +275,9 @@ static void launch_watch_w(Ctx* c, const WatchArgs& a) {
 }
 
 // after E_r: round r's arrivals at the watched peers, and their own first receipts
-int watch_count_round(Ctx* c) {
-  if (!c->watch_on || !c->watch_valid) return 0;
-  if (!c->d_frx[0] || c->frx_rows < c->n || c->watch_words != c->words)
-    return set_error(GP_ESTATE, "internal: watched peers without frontier rows");
+static int watch_count_round(Ctx* c) {
+  GP_TRY(record_need_rows(c, watch_record, c->n));
+  if (c->watch_words != c->words) return set_error(GP_ESTATE, "internal: watched peers at another row width");
   const int cur = c->cur;
   WatchArgs a{};
   a.wcol = c->d_watch_col;
@@ -301,33 +293,15 @@ int watch_count_round(Ctx* c) {
   a.arcs = c->watch_arcs;
   a.peers = (int32_t)c->h_watch_v.size();
   a.r = (uint32_t)c->round;
-  switch (c->words) {
-    case 1: launch_watch_w<1>(c, a); break;
-    case 2: launch_watch_w<2>(c, a); break;
-    case 4: launch_watch_w<4>(c, a); break;
-    case 8: launch_watch_w<8>(c, a); break;
-    case 16: launch_watch_w<16>(c, a); break;
-    case 32: launch_watch_w<32>(c, a); break;
-    case 64: launch_watch_w<64>(c, a); break;
-    default: return set_error(GP_EINVAL, "unsupported word count");
-  }
+  GP_TRY(with_words(c->words, [&](auto w) { launch_watch_w<w()>(c, a); }));
   GP_HIP(hipGetLastError());
   return 0;
 }
 
-// gp_checkpoint_load restored the run at `round`: the record is not in the blob
-void watch_restored(Ctx* c, int32_t round) {
-  if (c->watch_on && round > 0) c->watch_valid = false;
-}
-
-// the reads' common refusals (link_readable's)
-static int watch_readable(Ctx* c) {
-  if (c->nranks > 1) return set_error(GP_ENOTRACK, "watched peers are not kept by a vertex-partitioned context");
-  if (!c->watch_on || !state_ready(c)) return set_error(GP_ENOTRACK, "gp_watch, then gp_reset");
-  if (!c->watch_valid)
-    return set_error(GP_ESTATE, "the run was restored past round 0: its watched peers' record was not kept (gp_reset)");
-  return 0;
-}
+// (the request is gp_watch's list, not a flag)
+static bool watch_wanted(const Ctx* c) { return c->watch_want(); }
+GP_RECORD_OPS(watch_record) = {R_WATCH, "watched peers", "gp_watch", true, 6, watch_wanted, nullptr, watch_reset,
+                                watch_free, watch_count_round, watch_forget, nullptr};
 
 // `rows` record rows from `src` (device stride 64 W) to the host's m columns
 static int watch_copy_rows(Ctx* c, void* host, const uint8_t* src, int64_t rows) {
@@ -339,7 +313,7 @@ static int watch_copy_rows(Ctx* c, void* host, const uint8_t* src, int64_t rows)
 }
 
 int watch_read(Ctx* c, int32_t what, void* host, int64_t bytes) {
-  GP_TRY(watch_readable(c));
+  GP_TRY(record_readable(c, watch_record));
   const int64_t K = (int64_t)c->h_watch_v.size(), A = c->watch_arcs;
   const int64_t want = what == GP_WATCH_PTR ? (K + 1) * 8 : (what == GP_WATCH_FIRST ? K : A) * (int64_t)c->m;
   if (bytes != want) return set_error(GP_EINVAL, "bytes mismatch: expected " + std::to_string(want));
@@ -386,7 +360,7 @@ int gp_watch(gp_ctx* c, int32_t count, const int32_t* verts, int64_t max_bytes) 
 
 int gp_watch_info(gp_ctx* c, int32_t* count, int64_t* arcs, int64_t* bytes) {
   if (!c) return set_error(GP_EINVAL, "null ctx");
-  const bool on = c->watch_on && state_ready(c);
+  const bool on = c->rec[R_WATCH].on && state_ready(c);
   const int64_t K = on ? (int64_t)c->h_watch_v.size() : 0, A = on ? c->watch_arcs : 0;
   if (count) *count = (int32_t)K;
   if (arcs) *arcs = A;
@@ -396,7 +370,7 @@ int gp_watch_info(gp_ctx* c, int32_t* count, int64_t* arcs, int64_t* bytes) {
 
 int gp_read_watch_peer(gp_ctx* c, int32_t slot, void* first_row, void* arrival, int64_t arrival_bytes) {
   if (!c) return set_error(GP_EINVAL, "null ctx");
-  GP_TRY(watch_readable(c));
+  GP_TRY(record_readable(c, watch_record));
   if (slot < 0 || (size_t)slot >= c->h_watch_v.size()) return set_error(GP_EINVAL, "no such slot");
   const int64_t b = c->h_watch_ptr[(size_t)slot], deg = c->h_watch_ptr[(size_t)slot + 1] - b;
   if (arrival_bytes != deg * (int64_t)c->m)
