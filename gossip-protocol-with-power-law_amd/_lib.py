@@ -173,6 +173,9 @@ SIGNATURES = {
     "gp_link_loss_info": (ctypes.c_int, [_P, _PI32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]),
     "gp_link_delay": (ctypes.c_int, [_P, _I32, _I32, _U64]),
     "gp_link_delay_info": (ctypes.c_int, [_P, _PI32, _PI32, ctypes.POINTER(ctypes.c_uint64), _PI32]),
+    "gp_repair": (ctypes.c_int, [_P, _I32, _I32, _U64]),
+    "gp_repair_info": (ctypes.c_int, [_P, _PI32, _PI32, ctypes.POINTER(ctypes.c_uint64), _PI32]),
+    "gp_read_repair": (ctypes.c_int, [_P, ctypes.c_void_p, _I32, _PI32]),
     "gp_checkpoint_size":(ctypes.c_int, [_P, _PI64]),
     "gp_checkpoint_save": (ctypes.c_int, [_P, _P, _I64]),
     "gp_checkpoint_load": (ctypes.c_int, [_P, _P, _I64]),

@@ -244,6 +244,7 @@ int gp_checkpoint_load(gp_ctx* c, const void* host, int64_t bytes) {
   // no per-run record is in the blob (as the job record): a run
   // restored at round 0 has counted nothing yet and keeps the cleared ones
   records_restored(c, h.round);
+  repair_restored(c, h.round);   // (nor is the repair record; the setting is the context's, `quiet` restarts)
   return 0;
 }
 

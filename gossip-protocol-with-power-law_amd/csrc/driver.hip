@@ -451,7 +451,8 @@ static RoundFacts round_facts(const Ctx* c) {
   f.lp_env = c->lp_env;
   f.can_park = !c->carry.park_failed;
   f.carry = c->carry;
-  f.lossy = c->loss_on || c->lag_on;   // (delayed links read frontier rows through the same plan, delayed.hip)
+  // (delayed links read frontier rows through the same plan, delayed.hip; so does a run with repair, repair.hip)
+  f.lossy = c->loss_on || c->lag_on || c->repair_on;
   return f;
 }
 
@@ -540,6 +541,7 @@ static int round_launch(Ctx* c) {
   if (!state_ready(c) || c->words <= 0) return set_error(GP_ESTATE, "gp_set_messages + gp_reset first");
   if (c->round > 253) return set_error(GP_ESTATE, "round limit (254) reached");
   GP_TRY(lag_check_round(c));   // (delayed links: before anything of the round is enqueued)
+  GP_TRY(repair_check_round(c));
   GP_HIP(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   u64* stats = c->d_stats;
@@ -698,6 +700,7 @@ static int round_collect(Ctx* c, gp_round_stats* out) {
   c->prev_receivers = h[S_RECEIVERS];
   c->held_bits += h[S_INJECTED] + h[S_NEW_BITS];
   c->lag_hist = (c->lag_hist << 1) | (h[S_ACTIVE] ? 1u : 0u);   // (delayed links: lag_in_flight)
+  repair_collect(c, h, h[S_NEW_BITS], r);
   {   // what this round hands to the next one
     const RoundPlan& p = c->plan;
     RoundCarry& k = c->carry;
@@ -766,6 +769,7 @@ int gp_round(gp_ctx* c, gp_round_stats* out) {
   // (message-shard job, shard.hip: the history check and its growth come
   // first, so that no error of theirs can leave a round half applied)
   GP_TRY(lag_check_round(c));   // (delayed links are refused in a shard job: before its history moves)
+  GP_TRY(repair_check_round(c));   // (and so is repair)
   if (c->jnranks > 0) GP_TRY(shard_prepare_round(c));
   GP_TRY(round_launch(c));
   GP_TRY(round_exchange_rccl(c));
@@ -834,7 +838,10 @@ int gp_run(gp_ctx* c, int32_t max_rounds, gp_round_stats* per_round, int32_t* ro
     if (per_round) per_round[k] = st;
     ++done;
     // (delayed links: and nothing in flight -- no sender in the last dmax - 1 rounds)
-    if (st.new_bits == 0 && st.round >= c->last_inject_round && lag_in_flight(c) == 0) break;
+    // (repair: and the last `period` rounds were all silent -- at period 1 the same rule)
+    if (st.new_bits == 0 && st.round >= c->last_inject_round && lag_in_flight(c) == 0 &&
+        (!c->repair_on || c->repair_quiet >= c->repair_period))
+      break;
   }
   if (rounds_out) *rounds_out = done;
   return 0;

@@ -1098,6 +1098,8 @@ template <int W> void launch_acc_clear_w(Ctx* c);                     // ... and
 template <int W> void launch_apply_touched_w(Ctx* c, const ExpandArgs& a);   // the push's tail alone: touched list, receiver side
 // lossy.hip: an expansion round over lossy links (plan.pull.kernel == PULL_LOSSY)
 template <int W> void launch_expand_lossy_w(Ctx* c, const ExpandArgs& a);
+// repair.hip: a repair round of a run with anti-entropy repair in force (loss or none)
+template <int W> void launch_expand_repair_w(Ctx* c, const ExpandArgs& a);
 // delayed.hip: the same round with link delay in force (c->lag_on), loss or none
 template <int W> void launch_expand_delayed_w(Ctx* c, const ExpandArgs& a);
 // hub.hip: the hub receivers of a pull round -- the chunks' partial rows (on

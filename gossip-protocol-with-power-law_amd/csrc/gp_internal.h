@@ -35,8 +35,10 @@ enum StatSlot {
   // (partition.hip k_rx_unpack); all-reduced with the counters, fails the round
   S_XERR = NST + 1,
   S_REPORT_CURSOR = 26, S_CAND, S_ACTIVE_CURSOR, S_BIG_CURSOR, S_TOUCH_CURSOR, S_DET_BIG,
-  S_ULIST   // entries of the next round's receiver list (k_expand survivors)
+  S_ULIST,  // entries of the next round's receiver list (k_expand survivors)
+  S_REPAIR_X, S_REPAIR_LINES   // a repair round's exchanges and lines carried (k_repair_offer)
 };
+static_assert(S_REPAIR_LINES < 64, "the counter block read back each round holds 64 slots");
 static_assert(S_XERR < S_REPORT_CURSOR, "S_XERR must be inside the all-reduced counter slots");
 
 struct HubItem {       // one wave's share of a hub's in-list
@@ -256,6 +258,21 @@ struct Ctx {
   u64* d_lag_bits = nullptr;              // [lag_dmax + 1][lag_nw] k_mkbits' bitmap of round s in row s % lag_dmax; last row: their OR
   int64_t lag_nw = 0;                     // words per bitmap row
   uint8_t* d_lag_arc = nullptr;           // [nnz] d(u, v) per arc of the in-CSR
+  // anti-entropy repair (repair.hip): in every round r
+  // with (r + 1) % period == 0 each up receiver pulls the Message-List of one
+  // in-neighbour drawn from the receiver and the round.  repair_want /
+  // repair_period_want / repair_seed_want are what gp_repair asked for,
+  // repair_on / repair_period / repair_seed the setting of the run since the
+  // last gp_reset (single-rank contexts only, no shard job, no link delay)
+  bool repair_want = false, repair_on = false;
+  int32_t repair_period_want = 1, repair_period = 1;
+  uint64_t repair_seed_want = 0, repair_seed = 0;
+  int32_t repair_quiet = 0;               // most recent consecutive rounds >= the last inject round with no new bit
+  bool repair_rec_valid = true;           // false: the run was restored past round 0, its record is not kept
+  std::vector<uint64_t> repair_rec;       // [rounds][2] exchanges, lines per round since gp_reset
+  u64* d_rbits = nullptr;                 // [n_alloc/64] a repair round's receivers below hub_threshold whose
+                                          //   accumulator row holds an offer (written whole by k_repair_offer)
+  int64_t rbits_words = 0;
   bool holds_frx() const { return frx_users(this) != 0; }
   uint32_t* d_fpop[2] = {nullptr, nullptr};    // [n_alloc]
   int cur = 0;
@@ -510,6 +527,14 @@ int fresh_curve_env_grid();                    // GP_FRESH_CURVE_GRID in the env
 bool delay_env_rows();                         // GP_DELAY_ROWS=1 in the environment
 // lossy.hip
 int loss_reset(Ctx* c);                        // gp_reset: gp_link_loss takes effect, or the reset is refused
+// repair.hip
+int repair_check_reset(const Ctx* c);          // gp_reset, before anything changes: gp_repair's request can take effect, or the reset is refused
+int repair_reset(Ctx* c);                      // gp_reset: it takes effect; the mark bitmap, the record and `quiet` start over
+void repair_free(Ctx* c);
+int repair_check_round(const Ctx* c);          // before a round: GP_ESTATE when repair is in force in a shard job
+bool repair_now(const Ctx* c);                 // repair is in force and the context's round is a repair round
+void repair_collect(Ctx* c, const u64* h_stats, u64 new_bits, int32_t r);   // round_collect: the record's row, `quiet`
+void repair_restored(Ctx* c, int32_t round);   // gp_checkpoint_load: the record of a run restored past round 0 is not kept
 // delayed.hip
 int lag_reset(Ctx* c);                         // gp_reset, before anything changes: gp_link_delay's request can take effect, or the reset is refused
 int lag_prepare(Ctx* c);                       // gp_reset, with the run state in place: it takes effect; the ring, the bitmaps, the arc delays

@@ -36,51 +36,9 @@
 // and what gp_reset does with it (loss_reset).
 #include "gp_device.h"
 #include "link_loss.h"
+#include "lossy_scan.h"
 
 namespace gp {
-
-// one lossy round's arguments beside the pull's block (ExpandArgs stays as it
-// is, so every other kernel keeps its code)
-struct LossArgs {
-  const u64* __restrict__ frx;   // exact frontier rows of round r, valid behind fpop[u] != 0
-  LossDraw d;
-};
-
-// arcs [b, e) of receiver v's in-list: OR of the open live senders' frontier rows
-template <int W>
-__device__ __forceinline__ void lossy_scan(const ExpandArgs& a, const LossArgs& la, int v, int64_t b, int64_t e,
-                                           WaveLds& L, int lane, int g, int lw, u64x2& acc, WaveStats& st) {
-  constexpr int RPI = Geo<W>::RPI;
-  constexpr int RIF = RowsInFlight<W>::value;
-  for (int64_t j0 = b; j0 < e; j0 += 64) {
-    const int n = (int)min((int64_t)64, e - j0);
-    st.add(S_ARCS, n);
-    int32_t ent = -1;
-    if (lane < n && !la.d.closed) {
-      const int32_t u = a.col[j0 + lane];
-      // (a crash zeroes fpop before k_mkbits: a down vertex is no sender)
-      if (((a.abits[u >> 6] >> (u & 63)) & 1ull) && arc_open(la.d.key, (uint32_t)(a.vbegin + u), (uint32_t)(a.vbegin + v), la.d.thresh)) ent = u;
-    }
-    const int cnt = stage_pass(L, ent);
-    if (cnt == 0) continue;
-    for (int k0 = 0; k0 < cnt; k0 += RIF * RPI) {
-      u64x2 r[RIF];
-      u64 pieces = 0;
-#pragma unroll
-      for (int q = 0; q < RIF; ++q) {
-        const int k = k0 + g + q * RPI;
-        r[q] = u64x2{0, 0};
-        if (k < cnt) r[q] = load_piece<W>(la.frx, L.idx[k], lw);
-        pieces += line_pieces<W>(__ballot(k < cnt));
-      }
-#pragma unroll
-      for (int q = 0; q < RIF; ++q) acc |= r[q];
-      st.add(S_GATHERED, (u64)min(RIF * RPI, cnt - k0));
-      st.add(S_ROW_BYTES, pieces * (u64)(8 * Geo<W>::WPL));
-    }
-    wave_sync_lds();   // L.idx is restaged by the next pass
-  }
-}
 
 // Narrow rows (W <= 16): the receivers of in-degree <= GROUP_CHUNKS * LPR go
 // RPI per wave step, one per row slot, as k_apply_lanes takes the push's
@@ -293,6 +251,15 @@ __global__ __launch_bounds__(64) void k_hub_lossy(ExpandArgs a, LossArgs la) {
   flush_stats<1>(st, a.partial);
 }
 
+// the hub items' kernel alone (a repair round launches it behind its offers, repair.hip)
+template <int W>
+void launch_hub_lossy_w(Ctx* c, const ExpandArgs& a, const LossArgs& la) {
+  if (c->n_hub_items <= 0) return;
+  ExpandArgs h = a;
+  h.n_items = c->n_hub_items;
+  hipLaunchKernelGGL(k_hub_lossy<W>, dim3(grid_for(h.n_items, 1)), dim3(64), 0, c->stream, h, la);
+}
+
 template <int W>
 void launch_expand_lossy_w(Ctx* c, const ExpandArgs& a) {
   LossArgs la;
@@ -300,17 +267,14 @@ void launch_expand_lossy_w(Ctx* c, const ExpandArgs& a) {
   la.d = loss_draw(c->loss_p, c->loss_seed, (uint32_t)c->round);
   hipStream_t s = c->stream;
   (void)hipEventRecord(c->ev[4], s);
-  if (c->n_hub_items > 0) {   // first: their chains are the round's longest
-    ExpandArgs h = a;
-    h.n_items = c->n_hub_items;
-    hipLaunchKernelGGL(k_hub_lossy<W>, dim3(grid_for(h.n_items, 1)), dim3(64), 0, s, h, la);
-  }
+  launch_hub_lossy_w<W>(c, a, la);   // first: their chains are the round's longest
   if (a.nloc > 0)
     hipLaunchKernelGGL(k_expand_lossy<W>, dim3(grid_for(a.nloc, (int64_t)EWAVES * 64)), dim3(EBLOCK), 0, s, a, la);
   if (c->n_hub_items > 0) launch_apply_touched_w<W>(c, a);
   (void)hipEventRecord(c->ev[5], s);
 }
-#define V(W) template void launch_expand_lossy_w<W>(Ctx*, const ExpandArgs&);
+#define V(W) template void launch_expand_lossy_w<W>(Ctx*, const ExpandArgs&); \
+             template void launch_hub_lossy_w<W>(Ctx*, const ExpandArgs&, const LossArgs&);
 V(1) V(2) V(4) V(8) V(16) V(32) V(64)
 #undef V
 

@@ -485,6 +485,7 @@ static int launch_expand_w(Ctx* c, ExpandArgs a) {
   }
   if (c->plan.pull.kernel == PULL_LOSSY) {   // lossy links: a family of its own, none of the pull's passes (lossy.hip)
     if (c->lag_on) launch_expand_delayed_w<W>(c, a);   // delayed links, dmax = 1 included (delayed.hip)
+    else if (repair_now(c)) launch_expand_repair_w<W>(c, a);   // a repair round (repair.hip)
     else launch_expand_lossy_w<W>(c, a);
     return PULL_OK;
   }

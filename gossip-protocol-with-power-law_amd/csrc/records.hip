@@ -19,7 +19,7 @@ static bool record_needs_frx(const Ctx* c, const RecordOps& o) { return o.needs_
 uint32_t frx_users(const Ctx* c) {
   bool needs[R_COUNT];
   for (int k = 0; k < R_COUNT; ++k) needs[kRecords[k]->id] = record_needs_frx(c, *kRecords[k]);
-  return frx_mask(c->cfg.track_msg_forwards != 0, c->local, c->loss_want, c->lag_want, needs);
+  return frx_mask(c->cfg.track_msg_forwards != 0, c->local, c->loss_want || c->repair_want, c->lag_want, needs);   // (repair reads them as loss does)
 }
 
 int records_reset(Ctx* c) {

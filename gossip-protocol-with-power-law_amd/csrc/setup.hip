@@ -591,6 +591,7 @@ void gp_destroy(gp_ctx* c) {
   if (c->comm) (void)ncclCommDestroy(c->comm);
   shard_free(c);
   lag_release(c);
+  repair_free(c);
   dfree(&c->d_row_ptr); dfree(&c->d_col); dfree(&c->d_out_row_ptr); dfree(&c->d_out_col);
   dfree(&c->d_deg_out); dfree(&c->d_comp); dfree(&c->d_abits); dfree(&c->d_dbits); dfree(&c->d_lm); dfree(&c->d_lmw[0]); dfree(&c->d_lmw[1]); dfree(&c->d_sbits); dfree(&c->d_amask); dfree(&c->d_cml[0]); dfree(&c->d_cml[1]); dfree(&c->d_cmk[0]); dfree(&c->d_cmk[1]); dfree(&c->d_done_at);
   dfree(&c->d_done_at0); dfree(&c->d_cmask0); dfree(&c->d_lostcnt); dfree(&c->d_alive);
@@ -876,6 +877,7 @@ int gp_reset(gp_ctx* c) {
   if (!c) return set_error(GP_EINVAL, "null ctx");
   GP_HIP(hipSetDevice(c->device));
   GP_TRY(lag_reset(c));    // (gp_link_delay may refuse the reset, before anything changes; lag_prepare below applies it)
+  GP_TRY(repair_check_reset(c));   // (gp_repair may refuse it too; repair_reset below applies it)
   GP_TRY(loss_reset(c));   // (gp_link_loss takes effect here -- or refuses the reset, before anything changes)
   // (the records' requests, gp_link_loss and gp_link_delay take effect here: the frontier rows for who reads
   // them now, the spread curve's buffer)
@@ -927,6 +929,7 @@ int gp_reset(gp_ctx* c) {
   shard_reset(c);
   GP_TRY(records_reset(c));       // (every gp_track_* and gp_watch takes effect here)
   GP_TRY(lag_prepare(c));         // (and gp_link_delay: the ring of frontier rows, the arc delays)
+  GP_TRY(repair_reset(c));        // (and gp_repair: the mark bitmap, an empty record)
   GP_HIP(hipStreamSynchronize(s));
   return 0;
 }

@@ -641,6 +641,44 @@ class GossipEngine:
         row of j) while delay is in force (lag.arc_delays is its numpy twin)."""
         return self._read(_lib.ARC_DELAY, np.empty(self.info()[1], dtype=np.uint8))
 
+    # -- anti-entropy repair (csrc/repair.hip; helpers in repair.py) -----------
+    def repair(self, period, seed=0):
+        """gp_repair: from the next reset() on, every round r with
+        (r + 1) % period == 0 is a repair round, in which each up peer pulls
+        the whole Message-List of one in-neighbour drawn from the peer and the
+        round (repair.partners is its numpy twin) over that link, if the
+        round's loss draw leaves it open; repair(None) turns it off.  What it
+        brings is a first receipt like any other and is forwarded once.  run()
+        stops after `period` silent rounds, a loop over round() reads
+        repair_info()[3]; a silent period is the stopping rule, not
+        convergence.  reset() refuses repair together with link_delay, a
+        record that walks arcs (track_load, track_fresh, track_fresh_curve,
+        track_link_fresh, track_mult, watch), a vertex partition or a
+        message-shard job.  A period outside [1, 64] raises and leaves the
+        request as it was."""
+        if period is None:
+            check(self._lib.gp_repair(self._ctx, 0, 1, 0))
+        else:
+            check(self._lib.gp_repair(self._ctx, 1, int(period), int(seed) & ((1 << 64) - 1)))
+
+    def repair_info(self):
+        """(on, period, seed, quiet) of the setting in force for the current
+        run; quiet counts the most recent consecutive rounds at or after the
+        last inject round without a new bit."""
+        on, period, seed, quiet = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_uint64(), ctypes.c_int32()
+        check(self._lib.gp_repair_info(self._ctx, ctypes.byref(on), ctypes.byref(period), ctypes.byref(seed),
+                                       ctypes.byref(quiet)))
+        return bool(on.value), period.value, seed.value, quiet.value
+
+    def repair_record(self):
+        """u64 [R][2]: per round run since reset(), the exchanges that happened
+        and the Message-List entries they carried (both 0 outside the repair
+        rounds)."""
+        buf = np.zeros((254, 2), dtype=np.uint64)
+        k = ctypes.c_int32()
+        check(self._lib.gp_read_repair(self._ctx, _ptr(buf), 254, ctypes.byref(k)))
+        return buf[:k.value].copy()
+
     def _nv(self):   # per-vertex reads: the owned slice of a partitioned context
         return self.nloc() if self.nranks > 1 else self.n
 

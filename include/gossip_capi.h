@@ -856,6 +856,70 @@ int gp_link_loss_info(gp_ctx* ctx, int32_t* on, double* p, uint64_t* seed);
 int gp_link_delay(gp_ctx* ctx, int32_t on, int32_t dmax, uint64_t seed);
 int gp_link_delay_info(gp_ctx* ctx, int32_t* on, int32_t* dmax, uint64_t* seed, int32_t* in_flight);
 
+/* Anti-entropy repair (csrc/repair.hip, csrc/repair_draw.h; DESIGN.md §2.2,
+ * §2.6, §3.21).  Over lossy links a dropped line is lost for good.  With repair
+ * on, round r is a repair round iff (r + 1) % period == 0, period in [1, 64],
+ * and in one every up vertex v with an in-neighbour reconciles its whole
+ * Message-List with one of them:
+ *
+ *   p_r(v) = col[row_ptr[v] + below(draw(stream_key(seed, 0x400 + r), (uint64_t)v), deg_in(v))]
+ *
+ * v a global vertex id, the in-CSR as loaded or built (GP_ROW_PTR / GP_COL).
+ * The exchange happens iff p_r(v) is up in round r and arc p_r(v) -> v is open
+ * in round r (gp_link_loss's draw: always with loss off, never at p = 1; the
+ * exchange and the gossip line on the same arc in the same round share their
+ * fate).  It offers v the messages p_r(v) held before this round's receipts
+ * and v did not; they join the round's gossip: first receipts of receipt round
+ * r + 1 like any other, with a first byte and a digest term, and v forwards
+ * them once in round r + 1 -- repair restarts the flood.  `sends`, `active`
+ * and GP_FORWARDS need no new rule.  A self-loop partner offers nothing, a
+ * removed or crashed partner answers nothing, heartbeats are untouched.  The
+ * partner draw sees the receiver and the round only: a message table run in
+ * blocks (msg_word_base) gives the columns of the whole run, and no gp_config
+ * tuning field changes an output.  Without loss (or with p = 0) repair changes
+ * no first receipt: every message an up neighbour holds was sent to v in the
+ * round after that neighbour first held it.
+ *
+ * Termination: the run is over after the first round r whose last `period`
+ * rounds all lie at or after the last inject round and all have new_bits = 0
+ * (period 1: the flood's rule).  gp_run stops by this rule; a caller stepping
+ * gp_round reads `quiet` from gp_repair_info: the number of most recent
+ * consecutive rounds at or after the last inject round with new_bits = 0.
+ * With one random partner a silent period is NOT convergence: another draw
+ * could still repair something.  It is only the stopping rule.  The 254-round
+ * ceiling and its GP_ESTATE stay.
+ *
+ * gp_repair sets the request for the next gp_reset (on = 0: off; seed is then
+ * ignored).  GP_EINVAL for a period outside [1, 64], also with on = 0: the
+ * previous request stays.  gp_repair_info reports the setting in force for the
+ * current run (any pointer may be null).  gp_read_repair writes, for each round
+ * run since gp_reset (at most cap of them; *rounds gets their number), two
+ * exact counts: out[r][0] = exchanges that happened in round r, out[r][1] =
+ * the Message-List entries they carried (a bit gossip also delivered in that
+ * round counts).  Both are 0 in a non-repair round.  Over the blocks of a
+ * message table the lines add up and the exchanges are each block's own.
+ * GP_ENOTRACK with repair off, GP_ESTATE for a run restored from a checkpoint
+ * past round 0.
+ *
+ * gp_reset fails with GP_EINVAL, and changes nothing, when repair is requested
+ * together with gp_link_delay, with gp_track_load, gp_track_fresh,
+ * gp_track_fresh_curve, gp_track_link_fresh, gp_track_mult or gp_watch (with
+ * or without loss; gp_last_error names the record), in a vertex-partitioned
+ * context or in a message-shard job (gp_shard_*).  A shard transport joined
+ * after the reset makes every further gp_round fail with GP_ESTATE, before
+ * anything of the round is enqueued.  gp_track_curve, gp_track_delay,
+ * gp_track_delay_dist, track_first, track_digest, track_msg_forwards, coverage
+ * and forwards stay exact.  Every round of such a run reports
+ * gp_round_stats.mode = 2 and scan = 0, and the context keeps the exact
+ * frontier rows, as under gp_link_loss.
+ *
+ * Checkpoints: as for gp_link_loss.  The setting is not in the blob and the
+ * draw depends on the round alone; only the repair record is lost, and `quiet`
+ * restarts at 0. */
+int gp_repair(gp_ctx* ctx, int32_t on, int32_t period, uint64_t seed);
+int gp_repair_info(gp_ctx* ctx, int32_t* on, int32_t* period, uint64_t* seed, int32_t* quiet);
+int gp_read_repair(gp_ctx* ctx, uint64_t* out /* [cap][2] */, int32_t cap, int32_t* rounds);
+
 /* Checkpoints (no reference counterpart -- the
  * reference's peers keep no state across restarts).  Taken between rounds:
  * the blob holds the whole per-run state of this context (Message-List rows in
