@@ -31,6 +31,11 @@ Tables (table(pkg, g, kind, m)), STEP = the vertices a flood advances per round:
              to the origin, so the four vertices of LATE alone give a vertex
              at most four distinct delays.)
   "uniform"  every message at vertex 0 in round 0.
+  "leaves"   far_hubs only: origin[k] = 300 + k % 200, inject[k] = 128 +
+             (k // 2) % 120.  Every message starts late at a leaf of one of
+             the two hubs, so that under loss and repair (repair_long_cases.py)
+             the leaves hold what their hub still misses and the hubs get
+             non-empty offers in the rounds past 128.
 """
 import functools
 
@@ -96,6 +101,11 @@ def table(pkg, g, kind, m):
     """(origin, inject) int32 [m] of table `kind` on overlay g"""
     if kind == "uniform":
         return np.zeros(m, np.int32), np.zeros(m, np.int32)
+    if kind == "leaves":
+        if g.n != 500:
+            raise ValueError("the leaves table is far_hubs's")
+        k = np.arange(m)
+        return (300 + k % 200).astype(np.int32), (128 + (k // 2) % 120).astype(np.int32)
     if step_of(g) == 2:
         origin = np.asarray(pkg.overlay.random_origins(g.n, m, seed=m), np.int32).copy()
     else:

@@ -58,9 +58,12 @@ def partners(g, rseed, r):
     return out
 
 
-def run(g, origin, inject=None, p=0.0, seed=0, crash_at=None, max_rounds=254, period=0, rseed=0):
+def run(g, origin, inject=None, p=0.0, seed=0, crash_at=None, max_rounds=254, period=0, rseed=0,
+        quiet_reset_at=None):
     """lossy_ref.run's result plus "repair" (uint64 [rounds][2]: exchanges,
-    lines) and the two counts in every round's stats.  p = 0.0 is "loss off"."""
+    lines) and the two counts in every round's stats.  p = 0.0 is "loss off".
+    quiet_reset_at = c: the count of silent rounds starts over before round c
+    is counted -- what a checkpoint restored at round c does to the rule."""
     n = int(g.n)
     rp = np.asarray(g.row_ptr, np.int64)
     src = np.asarray(g.col, np.int64)
@@ -117,6 +120,8 @@ def run(g, origin, inject=None, p=0.0, seed=0, crash_at=None, max_rounds=254, pe
         st["new_bits"] = int(new.sum())
         st["receivers"] = int(new.any(axis=1).sum())
         stats.append(st)
+        if r == quiet_reset_at:
+            quiet = 0
         quiet = quiet + 1 if st["new_bits"] == 0 and r >= last else 0
         if quiet >= max(period, 1):
             break
